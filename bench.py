@@ -14,6 +14,10 @@ One bench step = one execution of the device-resident plan: free-propagator buil
 half steps + the lock-step PT sweep of every trajectory. Inputs (PT, operators, pulse samples) are
 resident in HBM before the timed region. value = whole-job useful trajectory-steps per second
 (n_traj * n_tau per GPU; the trunk re-propagation 0 -> t1 (<= 25.5 ps) is executed but not counted).
+
+A plain run sets up, warms up, times `--steps` steps and prints the result line (`ms_per_step` = wall time of one
+timed step). `--dump-outputs DIR` also writes the last timed step's outputs (dump_outputs). `--full` adds the legs
+that take runs of their own, after the timed region: `single_run` (one-trajectory latency) and `cpu_baseline`.
 """
 import argparse
 import json
@@ -192,6 +196,31 @@ def cpu_baseline(chi, target_s=15.0):
                       f"lockstep blocks of {CPU_BLOCK} trajectories"}
 
 
+DUMP_MAX_VALUES = 1 << 21   # complex values per dumped array: 32 MiB as float64 (re, im) pairs
+DUMP_SEED = 20240611
+
+
+def dump_outputs(dirpath, allout):
+    """--dump-outputs: what the last timed step computed, the flat complex128 output block a caller of the plan
+    receives (engine.split_output's layout: per trajectory n_tau + 1 rows of n_out values; all ranks in rank order), as
+    DIR/outputs.npy: float64 (n, 2) = (re, im). An output of more than DUMP_MAX_VALUES values is sampled at fixed
+    positions (seeded, sorted, the same for every run of the same arguments); DIR/outputs_index.npy holds the flat
+    positions (float64, exact below 2^53)."""
+    import torch
+    total = int(allout.numel())
+    if total > DUMP_MAX_VALUES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, size=DUMP_MAX_VALUES))
+        vals = allout[torch.from_numpy(idx).to(allout.device)]
+    else:
+        idx = np.arange(total)
+        vals = allout
+    vals = np.ascontiguousarray(torch.view_as_real(vals.contiguous()).cpu().numpy(), dtype=np.float64)
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "outputs.npy"), vals)
+    np.save(os.path.join(dirpath, "outputs_index.npy"), idx.astype(np.float64))
+    return {"dir": dirpath, "values": int(vals.shape[0]), "of": total, "sampled": total > DUMP_MAX_VALUES}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -207,7 +236,12 @@ def main():
                     help="multi-GPU partition (SURVEY.md §8e): scan = rank r runs scan points [r*scan, (r+1)*scan) with "
                          "the whole t1 grid; t1 = every rank runs the same scan points and its block of a t1 grid of "
                          "t1*world points")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the single-trajectory latency "
+                         "(single_run) and the CPU port on a sample of the workload (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/outputs.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     args = ap.parse_args()
 
@@ -284,6 +318,9 @@ def main():
                   "backend": (dist.get_backend() if dist is not None else None), "values": int(allout.numel()),
                   "bytes": int(allout.numel()) * 16, "ms": gather_ms,
                   "checksum": float(torch.view_as_real(allout).abs().sum())}
+        if args.dump_outputs:
+            gather["dump"] = dump_outputs(args.dump_outputs, allout)
+    del allout, local_out
 
     useful = n_traj * args.n_tau
     executed = plan.traj_steps()   # shared trunks (PQD_BRANCH) counted once per workgroup
@@ -336,7 +373,7 @@ def main():
             "frac": mf["executed_mfma_flop"] / (ms_sweep * 1e-3) / 1e12 / PEAK_FP64_TFLOPS,
             "mfma_busy_frac": mf["mfma_busy_frac"], "effective_clock_GHz": mf["effective_clock_GHz"],
             "source": mf["source"]}
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # the reference's single-run case (one trajectory of the same model, chi and length; outside the timed
         # region): a latency figure, carried by N2 split workgroups
         s_sys, s_grid, s_pt, s_rho0, s_ops, s_tr = build_workload(1, args.n_tau, args.chi, scan=1,
@@ -355,7 +392,7 @@ def main():
                               "sweep_ms": s_ms, "us_per_step": s_ms * 1e3 / (args.n_tau + 1),
                               "traj_steps_per_s": (args.n_tau + 1) / (s_ms * 1e-3),
                               "path": path, "split_fallbacks": fallbacks}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.chi, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(line), flush=True)

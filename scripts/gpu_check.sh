@@ -8,5 +8,5 @@ run() { local name=$1 lim=$2; shift 2; echo "== $name (limit ${lim}s)"; timeout 
 STEPS=${STEPS:-pytest,smoke,bench}
 [[ $STEPS == *pytest* ]] && run pytest_gpu 1200 python -m pytest tests -m gpu -q -x ${PYTEST_K:+-k "$PYTEST_K"} ${PYTEST_ARGS}
 [[ $STEPS == *smoke* ]] && run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-[[ $STEPS == *bench* ]] && run bench 900 python bench.py --steps ${BENCH_STEPS:-3} --warmup 1 ${BENCH_ARGS}
+[[ $STEPS == *bench* ]] && run bench 900 python bench.py --full --steps ${BENCH_STEPS:-3} --warmup 1 ${BENCH_ARGS}
 exit 0

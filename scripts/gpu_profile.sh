@@ -9,6 +9,6 @@ STEPS=${STEPS:-ablate,trace}
 [[ $STEPS == *ablate* ]] && run ablate 600 python scripts/profile_sweep.py ${ABL_ARGS}
 [[ $STEPS == *trace* ]] && run rocprof_trace 900 rocprofv3 --kernel-trace --stats -d gpurun_out/prof/trace -o run --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS}
 [[ $STEPS == *pmc* ]] && run rocprof_pmc 900 rocprofv3 --kernel-trace --pmc FETCH_SIZE WRITE_SIZE -d gpurun_out/prof/pmc -o run --output-format csv -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline ${BENCH_ARGS}
-[[ $STEPS == *bench* ]] && run bench 900 python bench.py --steps ${BENCH_STEPS:-3} --warmup 1 ${BENCH_FULL_ARGS}
+[[ $STEPS == *bench* ]] && run bench 900 python bench.py --full --steps ${BENCH_STEPS:-3} --warmup 1 ${BENCH_FULL_ARGS}
 find gpurun_out/prof -name "*.csv" | head -20
 exit 0

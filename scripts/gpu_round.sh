@@ -17,6 +17,6 @@ rc2=$?
 tail -12 $O/pytest_gpu.log
 case $rc2 in 0|1) ;; *) echo "suite rc=$rc2: stopping"; exit 1;; esac
 [ "$2" = "nobench" ] && exit $((rc | rc2))
-timeout -k 10 300 python bench.py > $O/bench.log 2>&1 || { echo "bench failed"; tail -20 $O/bench.log; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench.log 2>&1 || { echo "bench failed"; tail -20 $O/bench.log; exit 1; }
 tail -c 600 $O/bench.log
 exit $((rc | rc2))

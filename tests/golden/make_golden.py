@@ -21,6 +21,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, REPO)
 from oracle import fref  # noqa: E402
+sys.path.insert(0, HERE)
+from npz_lzma import savez_lzma  # noqa: E402
 
 REF_ROOT = "/root/reference"
 
@@ -80,7 +82,8 @@ def gen_fortran():
         opa, opb, opc = rand_op(dim, rng), rand_op(dim, rng), rand_op(dim, rng)
         maps = rand_lindblad_maps(n_tfull - 1, dim, dt, rng)
         res = fref.calc_onetime_parallel(F(maps), rho0, n_tau, dim, opa, opb, opc, time, time_sparse)
-        np.savez_compressed(os.path.join(HERE, f"fortran_onetime_d{dim}.npz"),
+        # dim 6: LZMA members keep the file below the 1 MiB limit of a committed file (npz_lzma.py)
+        (savez_lzma if dim == 6 else np.savez_compressed)(os.path.join(HERE, f"fortran_onetime_d{dim}.npz"),
                             dm_tl=maps, rho_init=rho0, n_tau=n_tau, opa=opa, opb=opb, opc=opc,
                             time=time, time_sparse=time_sparse, result=np.asarray(res))
         # --- calc_onetime_parallel_block (propagate_tau.f90:189)

@@ -497,7 +497,7 @@ def test_tl_dynmap_vs_reference_golden(golden_dir):
     at map sizes 4/16/25/36, including rank-deficient maps where the rcond=1e-12 cut-off drops 3 singular
     values (tests/golden/make_golden_tlmap.py, pyref_tools.npz)"""
     from pyaceqd_amd import tools as T
-    z = load(golden_dir, "pyref_tlmap.npz")
+    z = {**load(golden_dir, "pyref_tlmap.npz"), **load(golden_dir, "pyref_tlmap_d6.npz")}
     for name in ("d4", "d5", "d6", "rank2", "rank4"):
         got = T.calc_tl_dynmap_pseudo(z[f"{name}_dm"], z[f"{name}_times"])
         assert got.shape == z[f"{name}_tl"].shape
