@@ -208,6 +208,10 @@ int pqd_plan_info(const pqd_plan* plan, int32_t* path, int32_t* bt, int32_t* spl
 /* 1 when the plan builds its free propagators through pulse windows (half steps outside a system's first..last driven
  * half step are not built; its kernels read the idle operators there: DESIGN.md §4.2, PQD_WIN), else 0 */
 int pqd_plan_windows(const pqd_plan* plan, int32_t* on);
+/* 1 when the plan's batched sweep (PQD_PATH_BATCHED) runs the lean instance of the lock-step kernel: the one compiled
+ * for the headline configuration only (N^2 = 16, chi = 64, 8 trajectories per workgroup, default switches; DESIGN.md
+ * §4.1, PQD_SWEEP_LEAN=0 forces the general instance), else 0 */
+int pqd_plan_sweep_lean(const pqd_plan* plan, int32_t* on);
 /* average kernel durations (ms) of the executions since the last reset (the most recent 64 at most),
  * from HIP events on the launch stream: [0] free-propagator kernel, [1] sweep kernel; n = executions */
 int pqd_plan_timing(pqd_plan* plan, double* ms_free, double* ms_sweep, int32_t* n, int32_t reset);

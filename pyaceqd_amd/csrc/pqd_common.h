@@ -190,6 +190,8 @@ struct SweepParams {
     const double2* Fidle;    //   Widle = ovec . Midle [n_sys][n_out][N2]
     const double2* Widle;
     int colbig;              // N2 > 16 column phases: one pass over k for all of a wave's tiles (1, PQD_COLBIG; 0: per tile)
+    int lean;                // 1: the plan has the headline configuration, the batched sweep runs its lean instance
+                             //   (pt_sweep.hip LEAN; pqd_host.cpp sweep_lean_ok; PQD_SWEEP_LEAN=0: general instance)
 };
 
 // split groups with several trajectories per group (pt_msplit.hip)

@@ -635,6 +635,17 @@ static int plan_trunks(pqd_plan* P, pqd_ctx* ctx, int n_sys, const std::vector<s
     return PQD_OK;
 }
 
+// The lean instance of the batched sweep (pt_sweep.hip LEAN) is compiled for one configuration, the headline one:
+// N2 = 16, chi = 64, BT = 8, 3M unit-list PT rows with at most two units per wave (umax counts the list's end
+// marker too), 3M columns, fused half steps, traces one lane per (trajectory, output, row), no ablation. Every other
+// plan runs the general instance. PQD_SWEEP_LEAN=0 forces the general instance (A/B, tests).
+static bool sweep_lean_ok(const pqd_plan* P, const SweepParams& sp) {
+    if (const char* e = getenv("PQD_SWEEP_LEAN"); e && atoi(e) == 0) return false;
+    return P->N2 == 16 && P->CHI == 64 && P->BT == 8 && sp.pt_mode == 4 && sp.cmul3 == 1 && sp.fuse == 1 &&
+           sp.trpre == 1 && sp.ablate == 0 && sp.units && sp.umax >= 2 && sp.umax <= 3 &&
+           P->BT * sp.n_out * P->N2 <= 512;
+}
+
 // the trunk pre-pass launch parameters: the main sweep's, with the trunk trajectories and checkpoint map
 static void finalize_trunks(pqd_plan* P) {
     P->sp.ck = P->ck.p;
@@ -647,6 +658,7 @@ static void finalize_trunks(pqd_plan* P) {
     k.traj_sys = P->tk_tsys.p; k.wbeg = P->tk_wbeg.p; k.wend = P->tk_wend.p; k.woff = P->tk_woff.p;
     k.ev_start = P->tk_evstart.p; k.out = P->tk_out.p;
     k.ck_map = P->tk_ckmap.p; k.ck_stride = P->n_steps + 1;
+    k.lean = 0;
     const int nw = P->tk_BT * sweep_wpt(P->N2, P->tk_BT, P->CHI);
     k.units = (P->sp.units ? P->tk_units.p : nullptr);
     k.umax = (int)(P->tk_units.n / nw);
@@ -1174,6 +1186,7 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
     // a static bias between the grid halves gains nothing; profiles/r03/quad_prio.log)
     sp.qprio = 2;
     if (const char* e = getenv("PQD_QPRIO")) sp.qprio = atoi(e) & 3;
+    sp.lean = sweep_lean_ok(P, sp) ? 1 : 0;
     finalize_trunks(P);
     if (P->split) {
         HIPCHK(P->Xs.alloc((size_t)P->n_traj * 4 * N2 * P->CHI));  // split exchange: 2 slots of granules
@@ -1415,6 +1428,12 @@ int pqd_plan_copy_output(pqd_plan* P, void* dst, int64_t out_len) {
 int pqd_plan_windows(const pqd_plan* P, int32_t* on) {
     if (!P || !on) return fail(PQD_ERR_ARG, "NULL argument");
     *on = P->win.p ? 1 : 0;
+    return PQD_OK;
+}
+
+int pqd_plan_sweep_lean(const pqd_plan* P, int32_t* on) {
+    if (!P || !on) return fail(PQD_ERR_ARG, "NULL argument");
+    *on = (P->sp.lean && !P->nopt && !P->split && !P->msplit && !P->quad) ? 1 : 0;
     return PQD_OK;
 }
 

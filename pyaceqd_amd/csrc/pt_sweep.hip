@@ -39,6 +39,13 @@ struct SweepLayout {
 
 typedef double dbl4 __attribute__((ext_vector_type(4)));
 
+// load of launch-constant metadata at a wave-uniform address through the scalar cache
+__device__ __forceinline__ int ldc(const int* q) { return *(const __attribute__((address_space(4))) int*)q; }
+__device__ __forceinline__ int4 ldc(const int4* q) {
+    const int* w = (const int*)q;
+    return make_int4(ldc(w), ldc(w + 1), ldc(w + 2), ldc(w + 3));
+}
+
 // Column phase on the matrix cores: one wave applies the N2 x N2 operator Op (row-major, complex) to
 // all CHI bond columns of its trajectory's augmented state S (LDS, row stride RS):
 //   C[N2 x CHI] = Op[N2 x N2] . S[N2 x CHI]   as v_mfma_f64_16x16x4_f64 tiles,
@@ -430,13 +437,21 @@ __device__ __forceinline__ void pt_row_mfma16(const double2* __restrict__ Qg, do
 // Reads every half step's M, F, W as stored: plans running this kernel (main sweep or trunk pre-pass) build the free
 // propagators without pulse windows (pqd_host.cpp). A window-select form of these loads measured 1.8% slower on the
 // bench launch even with its selects folded away at compile time (202.3 vs 198.1 ms, profiles/r02/windows/).
-template <int N2, int CHI, int BT, bool TRUNK>
+// LEAN: the headline instance (N2 = 16, chi = 64, BT = 8) with the A/B switches of SweepParams fixed at their production
+// values (3M unit-list PT rows, 3M columns, fused half steps, lane traces, no ablation), so its register allocation
+// is that of the one path it runs and not the maximum over all of them; the host selects it only for plans with
+// exactly that configuration (pqd_host.cpp sweep_lean_ok). With that room the wave's unit list and the slice schedule
+// stay in scalar registers (200.3 -> 196.1 ms per bench launch; the instance alone gains nothing, and
+// a register for the next event step or the first slice k-step loaded before the PT barrier measured slower).
+template <int N2, int CHI, int BT, bool TRUNK, bool LEAN = false>
 __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_kernel(SweepParams p, const double2* __restrict__ Mg,
                                                            const double2* __restrict__ Qg0, double2* __restrict__ outg,
                                                            const double2* __restrict__ Fg, const double2* __restrict__ Wg) {
     using L = SweepLayout<N2, CHI, BT>;
+    static_assert(!LEAN || (N2 == 16 && CHI == 64 && BT == 8 && !TRUNK), "the lean instance is the headline shape only");
     constexpr int RS = L::RS, TS = L::TS, KD = L::KD, NCOL = L::NCOL;
     constexpr int WPT = L::WPT, NW = L::NW, NT = 64 * NW;  // waves per trajectory, waves, threads
+    const int ablate = LEAN ? 0 : p.ablate;
     extern __shared__ __attribute__((aligned(16))) double2 smem[];
     double2* st = smem;
     double2* rbuf = smem + BT * TS;
@@ -496,8 +511,8 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
     // ---- column phases: wave w owns trajectory w % BT (its free propagators, its MTO events), and with two
     // waves per trajectory the column tiles of half w / BT
     double2* stw = st + tw * TS;
-    const bool c3 = p.cmul3 != 0;
-    const bool cbig = p.colbig != 0;
+    const bool c3 = LEAN || p.cmul3 != 0;
+    const bool cbig = !LEAN && p.colbig != 0;
     auto col = [&](const double2* __restrict__ Op) {
         if (c3) {
             if constexpr (col_big_ok<N2, CHI, RS, WPT>()) {
@@ -525,13 +540,23 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
     // traces with one lane per (trajectory, output, row) when N2 is a power of two and they fit the workgroup
     // (16-lane reduction groups); each lane keeps the next step's W row element in a register
     const int ntr = BT * p.n_out * N2;
-    const bool lanetr = (N2 == 4 || N2 == 16) && p.trpre && ntr <= NT;
+    const bool lanetr = LEAN || ((N2 == 4 || N2 == 16) && p.trpre && ntr <= NT);
     double2 wpre = c_zero();
     if (n0 > 0 && lanetr && tid < ntr) {  // the step the loop starts at: W(n0) row element, as fetched a step ahead
         const int a = tid % N2, bk = tid / N2, b = bk / p.n_out, k = bk - (bk / p.n_out) * p.n_out;
         wpre = Wg[(size_t)s_sys[b] * p.w_stride + ((size_t)n0 * p.n_out + k) * N2 + a];
     }
     bool fz = false;  // this wave's trajectory sits between M_b(n-1) and M_a(n) unapplied (fused step n)
+    // lean: this wave's PT units (at most two, pqd_host.cpp) and the slice schedule around the current step, loaded
+    // once or a step ahead through the scalar cache (the host wrote them before the launch; nothing here writes them)
+    int4 u0 = make_int4(-1, 0, -1, -1), u1 = u0;
+    int sc_prev = 0, sc_cur = 0, sc_nxt = 0;  // sched[n - 1], sched[n], sched[n + 1] (clamped to the schedule)
+    if constexpr (LEAN) {
+        u0 = ldc(p.units + (size_t)wave * p.umax);
+        u1 = ldc(p.units + (size_t)wave * p.umax + 1);
+        sc_prev = ldc(p.sched + (n0 > 0 ? n0 - 1 : 0));
+        sc_cur = ldc(p.sched + (n0 < p.n_steps ? n0 : p.n_steps - 1));
+    }
     for (int n = n0;; ++n) {
         // ------------------------------------------------------------ shared-trunk activations at step n
         if (n == next_act) {
@@ -578,8 +603,8 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
         bool need = false;
 #pragma unroll
         for (int b = 0; b < BT; ++b) need |= (s_wb[b] <= n) & (n <= s_we[b]);
-        if (need && !(p.ablate & 4)) {
-            const double2* cvec = (n == 0) ? p.closure0 : p.closure + (size_t)p.sched[n - 1] * CHI;
+        if (need && !(ablate & 4)) {
+            const double2* cvec = (n == 0) ? p.closure0 : p.closure + (size_t)(LEAN ? sc_prev : p.sched[n - 1]) * CHI;
             constexpr int NPART = BT * N2 * 4;
             for (int it = 0; it < (NPART + NT - 1) / NT; ++it) {
                 const int e = tid + NT * it;
@@ -633,6 +658,7 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
             }
         }
         if (n >= n_end) break;
+        if constexpr (LEAN) sc_nxt = ldc(p.sched + (n + 1 < p.n_steps ? n + 1 : p.n_steps - 1));
         if (lanetr && tid < ntr) {  // W(n + 1) row element for the next step's traces (fused trajectories)
             const int a = tid % N2, bk = tid / N2, b = bk / p.n_out, k = bk - (bk / p.n_out) * p.n_out;
             wpre = Wg[(size_t)s_sys[b] * p.w_stride + ((size_t)(n + 1) * p.n_out + k) * N2 + a];
@@ -640,7 +666,7 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
 
         // ------------------------------------------------------------ column phase A
         const double2* Ma = Mg + (size_t)(2 * n) * N2 * N2;
-        if (!(p.ablate & 2) && n >= my_act) {
+        if (!(ablate & 2) && n >= my_act) {
             const bool mto_now = ev_cur < ev_lim && p.ev[ev_cur].x == n;
             if (fz && !mto_now) {  // no MTO at step n: M_b(n-1) and M_a(n) in one operator
                 col(Fg + (size_t)n * N2 * N2);
@@ -659,7 +685,16 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
         __syncthreads();
 
         // ------------------------------------------------------------ PT contraction
-        if (!(p.ablate & 1)) {
+        if constexpr (LEAN) {
+            // 3M rows of this wave's one or two units, one k-step of the slice in flight (the default below)
+            const double2* Qs = Qg0 + (size_t)sc_cur * p.D * CHI * CHI;
+#pragma nounroll
+            for (int u = 0; u < 2; ++u) {
+                const int4 e = u ? u1 : u0;
+                if (e.x < 0) break;
+                pt_rows3<N2, CHI, BT, RS, TS, 1>(Qs + (size_t)e.x * CHI * CHI, st, e, lane);
+            }
+        } else if (!(ablate & 1)) {
             const double2* Qs = Qg0 + (size_t)p.sched[n] * p.D * CHI * CHI;
             // pt_mode 0: VALU rows, 1: matrix-core rows (4x4x4_4b), 4: matrix-core rows with 3 real products per
             // complex product (default), 3: split-complex 16x16x4 rows (BT = 8), 2: mixed (waves 0..NW/2-1 start on the matrix cores,
@@ -772,8 +807,8 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
         // ------------------------------------------------------------ column phase B
         const double2* Mb = Ma + N2 * N2;
         // fuse M_b(n) into the next step's operator unless this trajectory has an MTO at step n+1
-        fz = p.fuse && !(ev_cur < ev_lim && p.ev[ev_cur].x == n + 1);
-        if (!(p.ablate & 2) && !fz && n >= my_act) {
+        fz = (LEAN || p.fuse) && !(ev_cur < ev_lim && p.ev[ev_cur].x == n + 1);
+        if (!(ablate & 2) && !fz && n >= my_act) {
             col(Mb);
             while (ev_cur < ev_lim) {  // applyBefore-true MTOs at step n+1
                 const int4 e = p.ev[ev_cur];
@@ -783,6 +818,7 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
             }
         }
         if (lane == 0 && half == 0) s_fz[tw] = fz ? 1 : 0;
+        if constexpr (LEAN) { sc_prev = sc_cur; sc_cur = sc_nxt; }
         __syncthreads();
     }
 }
@@ -854,19 +890,21 @@ __global__ __launch_bounds__(64) void sweep_nopt_kernel(SweepParams p) {
     }
 }
 
-template <int N2, int CHI, int BT, bool TRUNK>
+template <int N2, int CHI, int BT, bool TRUNK, bool LEAN = false>
 hipError_t launch_sw(int n_blocks, const SweepParams& p, hipStream_t s) {
     using L = SweepLayout<N2, CHI, BT>;
     static_assert(L::LDS <= 160 * 1024, "LDS budget");
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)pt_sweep_kernel<N2, CHI, BT, TRUNK>,
+    static unsigned attr = 0;  // per-device bitmask (the attribute belongs to the device's copy of the kernel)
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
+    if (dev >= 32 || !(attr & (1u << dev))) {
+        hipError_t e = hipFuncSetAttribute((const void*)pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::LDS);
         if (e != hipSuccess) return e;
-        attr = true;
+        if (dev < 32) attr |= 1u << dev;
     }
-    hipLaunchKernelGGL((pt_sweep_kernel<N2, CHI, BT, TRUNK>), dim3(n_blocks), dim3(64 * L::NW), L::LDS, s, p, p.M, p.Q,
-                       p.out, p.F, p.W);
+    hipLaunchKernelGGL((pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN>), dim3(n_blocks), dim3(64 * L::NW), L::LDS, s, p, p.M,
+                       p.Q, p.out, p.F, p.W);
     return hipGetLastError();
 }
 
@@ -911,7 +949,9 @@ hipError_t launch_sweep(int N2, int CHI, int BT, int n_blocks, const SweepParams
         switch (N2) {
             case 4: return launch_sw_chi<4, 8>(CHI, n_blocks, p, s);
             case 9: return launch_sw_chi<9, 8>(CHI, n_blocks, p, s);
-            case 16: return launch_sw_chi<16, 8>(CHI, n_blocks, p, s);
+            case 16:
+                if (p.lean && CHI == 64) return launch_sw<16, 64, 8, false, true>(n_blocks, p, s);
+                return launch_sw_chi<16, 8>(CHI, n_blocks, p, s);
             default: return hipErrorInvalidValue;
         }
     }

@@ -383,6 +383,13 @@ class Plan:
         _lib.check(_lib.lib().pqd_plan_windows(self.handle, C.byref(on)))
         return bool(on.value)
 
+    def sweep_lean(self):
+        """True when the batched sweep runs the lean instance of the lock-step kernel (the headline configuration
+        only: N = 4, chi = 64, 8 trajectories per workgroup, default switches; PQD_SWEEP_LEAN=0 forces the general one)"""
+        on = C.c_int32()
+        _lib.check(_lib.lib().pqd_plan_sweep_lean(self.handle, C.byref(on)))
+        return bool(on.value)
+
     def traj_steps(self):
         """trajectory-steps one execute propagates (shared trunks counted once per workgroup)"""
         p, b, f, n = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
