@@ -212,6 +212,12 @@ int pqd_plan_windows(const pqd_plan* plan, int32_t* on);
  * for the headline configuration only (N^2 = 16, chi = 64, 8 trajectories per workgroup, default switches; DESIGN.md
  * §4.1, PQD_SWEEP_LEAN=0 forces the general instance), else 0 */
 int pqd_plan_sweep_lean(const pqd_plan* plan, int32_t* on);
+/* every decision plan creation took, as one line of space-separated key=value pairs in a fixed order: the device's
+ * CU count, path (PQD_PATH_*), workgroup shape, split / quad / multi-trajectory split / trunk layout, windows, the
+ * A/B switches as the kernels will see them, and 64-bit FNV-1a hashes (hex) of the block arrays, the PT row-unit list
+ * and the multi-trajectory group tables (0 where the plan has none). The decisions set speed, not results; tests pin
+ * them with this line. PQD_ERR_ARG if the line and its terminating NUL do not fit len bytes */
+int pqd_plan_describe(const pqd_plan* plan, char* buf, int32_t len);
 /* average kernel durations (ms) of the executions since the last reset (the most recent 64 at most),
  * from HIP events on the launch stream: [0] free-propagator kernel, [1] sweep kernel; n = executions */
 int pqd_plan_timing(pqd_plan* plan, double* ms_free, double* ms_sweep, int32_t* n, int32_t reset);

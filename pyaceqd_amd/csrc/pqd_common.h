@@ -321,9 +321,9 @@ hipError_t launch_map_tail(int N2, const double2* M, const double2* X, int n_x, 
                            double2* out, hipStream_t s);
 hipError_t launch_tl_dynmap(const double2* dm, int n_maps, int n, double rcond, double2* out, hipStream_t s);
 int tl_dynmap_nmax();
-bool split_supported(int N2, int CHI, int n_traj, int n_cu);
-int split_group_size(int N2);  // workgroups per split group (N2, or N2 + 1 with the output workgroup)
-bool split_ow_env();
+// ow: split groups have the output workgroup (SweepParams.split_ow; pqd_host.cpp PlanEnv)
+bool split_supported(int N2, int CHI, int n_traj, int n_cu, bool ow);
+int split_group_size(int N2, bool ow);  // workgroups per split group (N2, or N2 + 1 with the output workgroup)
 int split_blocks_per_cu(int N2, int CHI);
 hipError_t launch_split(int N2, int CHI, int n_traj, const SweepParams& p, double2* X, unsigned* cnt,
                         unsigned* err, hipStream_t s, int chunk = 0);

@@ -226,6 +226,14 @@ struct Carve {
         return r;
     }
 };
+
+// 64-bit FNV-1a over a host array's bytes, chained through h (the table hashes of pqd_plan_describe)
+template <class T>
+uint64_t fnv1a(const std::vector<T>& v, uint64_t h = 14695981039346656037ull) {
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(v.data());
+    for (size_t i = 0; i < v.size() * sizeof(T); ++i) h = (h ^ b[i]) * 1099511628211ull;
+    return h;
+}
 }  // namespace
 
 struct pqd_pt {
@@ -289,6 +297,10 @@ struct pqd_plan {
     DevBuf<double2> table;
     DevBuf<unsigned> flags;       // bit 0: non-finite output (PQD_ERR_NUMERIC)
     int split_fallbacks = 0;      // split launches that timed out and were re-run on the batched kernel
+    // pqd_plan_describe: the device's CU count and FNV-1a hashes of the block arrays, the PT row-unit list and the
+    // multi-trajectory group tables as uploaded (0: the plan has none)
+    int n_cu = 0;
+    uint64_t h_blocks = 0, h_units = 0, h_groups = 0;
     // hipEvent triplets (start, free propagators done, sweep done) of the last RING executes, created once
     static constexpr int RING = 64;
     hipEvent_t ring[3 * RING] = {};
@@ -439,6 +451,59 @@ int pqd_pt_create(pqd_ctx* ctx, int32_t dim, const pqd_pt_desc* d, pqd_pt** out)
 
 void pqd_pt_destroy(pqd_pt* pt) { delete pt; }
 
+// Every PQD_* switch that plan creation and pqd_free_propagators read (A/B only: the defaults are the measured-best
+// paths; INTEGRATION.md "Runtime switches", in that order). read_plan_env() is the only getenv of the plan code. It
+// runs once per pqd_plan_create_multi / pqd_free_propagators call and its result is never kept across calls: tests
+// flip switches between plans of one process. Each field keeps the form its reader always parsed: the raw integer,
+// "not 0", "exactly 1", or "set at all" (an extra value or flag for unset). The switches read in several places
+// (PQD_SPLIT, PQD_MSPLIT, PQD_FUSE, PQD_SPLIT_XCD, PQD_TRUNK, PQD_QUAD, PQD_WIN) gave every reader the same value, so
+// each has one field.
+struct PlanEnv {
+    int split, msplit, ms_tb, ms_ptm, fp4, fpm, pt_mode, cmul3, trpre, bt, colbig, trunk, quad, qpw, qcg, qprio, win,
+        rowpair, ablate;
+    bool ms_l2, split_ow, split_gran, split_xcd, sweep_lean, pt_mode_set, fuse, branch, idle, unitbal, split_l2;
+    unsigned split_spin;
+};
+
+static PlanEnv read_plan_env() {
+    auto num = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+    auto set = [](const char* name) { return getenv(name) != nullptr; };
+    PlanEnv v;
+    v.split = num("PQD_SPLIT", 1);              // single-trajectory split groups: 0 off, 1 auto, 2 whenever they fit
+    v.msplit = num("PQD_MSPLIT", 1);            // multi-trajectory split groups: 0 off, 1 auto, 2 whenever supported
+    v.ms_tb = num("PQD_MS_TB", 0);              // at least this many trajectories per group (unset: as few as fit)
+    v.ms_ptm = set("PQD_MS_PTM") ? num("PQD_MS_PTM", 0) != 0 : -1;  // their PT rows on the VALU (0) / matrix cores (1); -1 unset
+    v.ms_l2 = num("PQD_MS_L2", 1) != 0;         // exchange lines kept in L2 on the XCD-grouped grid (0: sc1 stores)
+    v.split_gran = num("PQD_SPLIT_GRAN", 0) == 1;  // 1: data-tagged granule exchange instead of the arrival counter
+    v.split_ow = !v.split_gran && num("PQD_SPLIT_OW", 1) != 0;  // output workgroup per split group (counter form only)
+    v.split_xcd = num("PQD_SPLIT_XCD", 1) != 0;  // each group's workgroups on one XCD (0: the plain grid)
+    v.fp4 = num("PQD_FP4", 1) != 0;             // N2 = 4 free propagators, 16 matrices per workgroup (0: general kernel)
+    v.fpm = num("PQD_FPM", 1);                  // N2 = 25, 36 free propagators on the matrix cores (raw value; 0: LDS)
+    v.sweep_lean = num("PQD_SWEEP_LEAN", 1) != 0;  // the lean sweep instance where the plan allows it (sweep_lean_ok)
+    v.pt_mode_set = set("PQD_PT_MODE");
+    v.pt_mode = num("PQD_PT_MODE", 0);          // PT-row variant (raw value; unset: 5 at BT = 4, else 4)
+    v.cmul3 = num("PQD_CMUL3", 1);              // 3M column products (raw value)
+    v.fuse = num("PQD_FUSE", 1) != 0;           // fused half steps F(n), W(n)
+    v.trpre = num("PQD_TRPRE", 1);              // prefetched trace rows (raw value; needs fused half steps)
+    v.bt = set("PQD_BT") ? (num("PQD_BT", 0) >= 8 ? 8 : 4) : 0;  // trajectories per workgroup, 4 or 8 (0: unset, auto)
+    v.colbig = num("PQD_COLBIG", 1);            // N2 > 16 column phases in one piece (raw value; 0: tile by tile)
+    v.branch = num("PQD_BRANCH", 1) != 0;       // shared trunks inside lock-step workgroups
+    v.trunk = num("PQD_TRUNK", -1);             // trunk pre-pass: -1 auto (by estimated time), 1 always, 0 never
+    v.quad = num("PQD_QUAD", 1);                // two-level quads: 0 off, 1 auto, 2 also at chi = 64
+    v.qpw = set("PQD_QPW") ? std::max(1, num("PQD_QPW", 1)) : 0;  // quads per workgroup (0: unset, by chi)
+    v.qcg = !set("PQD_QCG") ? 0 : num("PQD_QCG", 4) == 2 ? 2 : num("PQD_QCG", 4) == 1 ? 1 : 4;  // 4-column groups per wave: 2, 4, 1 (chi = 32 only); 0: unset
+    v.qprio = num("PQD_QPRIO", 2) & 3;          // quad wave priorities (2: raised outside the PT contraction)
+    v.idle = num("PQD_IDLE", 1) != 0;           // idle half steps copy one operator (0: compute every half step)
+    v.win = num("PQD_WIN", 1);                  // pulse windows: 0 never, 1 when they leave out a tenth, 2 always
+    v.unitbal = num("PQD_UNITBAL", 1) != 0;     // PT row units split to balance the waves (0: whole units)
+    v.rowpair = set("PQD_ROWPAIR") ? num("PQD_ROWPAIR", 1) != 0 : -1;  // 0: one PT row per unit; -1 unset
+    v.ablate = num("PQD_ABLATE", 0);            // kernel phase ablation and stamps (raw value; measurements only)
+    const char* spin = getenv("PQD_SPLIT_SPIN");
+    v.split_spin = spin ? (unsigned)strtoul(spin, nullptr, 10) : (1u << 22);  // polls before a split wait times out (~0.1 s)
+    v.split_l2 = num("PQD_SPLIT_L2", 1) != 0;   // split exchange lines kept in L2 (0: sc1 stores)
+    return v;
+}
+
 int pqd_free_propagators(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* grid, pqd_c128* M_out) {
     if (!ctx || !M_out) return fail(PQD_ERR_ARG, "NULL argument");
     int rc = check_system(sys);
@@ -455,9 +520,10 @@ int pqd_free_propagators(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* gr
     FreePropParams fp{};
     fp.systems = tab.p; fp.n_sys = 1;
     fp.ta = grid->ta; fp.dt = grid->dt; fp.n_steps = grid->n_steps; fp.n_sub = grid->n_sub; fp.M = M.p;
-    { const char* f4 = getenv("PQD_FP4"); fp.packed4 = (f4 && atoi(f4) == 0) ? 0 : 1; }
-    { const char* fm = getenv("PQD_FPM"); fp.mfma = fm ? atoi(fm) : 1; }
-    if (const char* ie = getenv("PQD_IDLE"); !(ie && atoi(ie) == 0)) {
+    const PlanEnv env = read_plan_env();
+    fp.packed4 = env.fp4;
+    fp.mfma = env.fpm;
+    if (env.idle) {
         HIPCHK(Mi.alloc((size_t)N2 * N2));
         fp.Midle = Mi.p;
     }
@@ -472,7 +538,7 @@ int pqd_free_propagators(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* gr
 // read of a slice feeds all of them. Units (cost = rows) go to the least-loaded wave, largest first. A unit is
 // (slice, row 0, row 1 or -1, row 2 | row 3 << 16 or -1, a missing row 3 being 0x7FFF); each wave's list ends
 // with slice -1.
-static std::vector<int4> pt_row_units(const std::vector<int>& gmap, int NW, int rmax) {
+static std::vector<int4> pt_row_units(const std::vector<int>& gmap, int NW, int rmax, bool balance) {
     const int N2 = (int)gmap.size();
     std::vector<int4> units;
     std::vector<int> done(N2, 0);
@@ -495,7 +561,7 @@ static std::vector<int4> pt_row_units(const std::vector<int>& gmap, int NW, int 
     // instead of 8 (one wave held two 4-row units). Least-loaded first, so the two waves of a SIMD (w, w + NW / 2)
     // also stay balanced: their MFMAs share its matrix pipe
     int T = (N2 + NW - 1) / NW;
-    if (const char* e = getenv("PQD_UNITBAL"); e && atoi(e) == 0) T = 1 << 20;  // A/B: whole units, least loaded
+    if (!balance) T = 1 << 20;  // PQD_UNITBAL=0 (A/B): whole units, least loaded
     std::vector<int> pending;  // rows of split units, slice-ordered
     for (const int4& e : units) {
         int w = -1;
@@ -558,14 +624,36 @@ static void branch_slots(int BT, const int* members, const std::vector<int>& jv,
     }
 }
 
+// What plan creation asks of the device: the CU count and the workgroups per CU the runtime reports for the two split
+// kernels. The queries are function pointers, so each is made only where its path is considered (PQD_SPLIT=0 asks
+// nothing) and a host-only test can drive choose_path with numbers of its own.
+struct DeviceCaps {
+    int n_cu;
+    int (*split_blocks_per_cu)(int N2, int CHI), (*msplit_blocks_per_cu)(int N2, int CHI);
+};
+
+// Single-trajectory split groups the device holds at once. The spin hand-off needs every workgroup of a launch
+// resident, by the occupancy the runtime reports for the split kernel. A batch just above `fit` runs as consecutive
+// co-resident launches, up to 4 at N2 >= 25 and 2 below, where they still beat one batched pass (a group step is
+// 3.6x / 2.4x faster than a batched block's; C5: 8 six-level trunks = 288 workgroups -> 7 + 1).
+struct SplitCap {
+    int slots, fit, launches;  // workgroups and groups resident at once; launches in a row that still pay
+    bool takes(int N2, int CHI, int n, int max_launches, bool ow) const {  // n groups in at most max_launches launches
+        return fit >= 1 && split_supported(N2, CHI, std::min(n, fit), slots, ow) && n <= max_launches * fit;
+    }
+};
+static SplitCap split_capacity(int N2, int CHI, bool ow, const DeviceCaps& caps) {
+    const int bpc = caps.split_blocks_per_cu(N2, CHI), slots = caps.n_cu * bpc;
+    return {slots, bpc >= 1 ? slots / split_group_size(N2, ow) : 0, N2 >= 25 ? 4 : 2};
+}
+
 // Trunk pre-pass of a plan: one MTO-free trajectory per system that has checkpoints, propagated from step 0 to
 // its last checkpoint step, writing the augmented state at the top of every checkpoint step (ck_steps[y], indices
 // ck_base[y] + k). It runs before the main sweep on split groups when those fit (N2 >= 9, as in auto mode), else
 // as batched workgroups of four; the batched layout is always built (fallback after a split timeout).
-static int plan_trunks(pqd_plan* P, pqd_ctx* ctx, int n_sys, const std::vector<std::vector<int>>& ck_steps,
-                       const std::vector<int>& ck_base, int n_ck, int n_cu, int N2, int n_out, const pqd_pt* pt,
-                       hipStream_t s) {
-    const int ns = P->n_steps, CHI = P->CHI;
+static int plan_trunks(pqd_plan* P, const std::vector<std::vector<int>>& ck_steps, const std::vector<int>& ck_base,
+                       int n_ck, const pqd_pt* pt, const PlanEnv& env, const DeviceCaps& caps, hipStream_t s) {
+    const int ns = P->n_steps, CHI = P->CHI, N2 = P->N2, n_out = P->n_out, n_sys = P->n_sys;
     std::vector<int> wb, we, ts, map;
     std::vector<long long> wo;
     for (int y = 0; y < n_sys; ++y) {
@@ -615,23 +703,16 @@ static int plan_trunks(pqd_plan* P, pqd_ctx* ctx, int n_sys, const std::vector<s
     HIPCHK(P->tk_blk_src.upload(bsrc.data(), bsrc.size(), s));
     {
         const int nw = BT * sweep_wpt(N2, BT, CHI);
-        std::vector<int4> u = pt_row_units(pt->gmap_h, nw, sweep_rmax(N2, BT, CHI));
+        std::vector<int4> u = pt_row_units(pt->gmap_h, nw, sweep_rmax(N2, BT, CHI), env.unitbal);
         HIPCHK(P->tk_units.upload(u.data(), u.size(), s));
     }
-    const int bpc = split_blocks_per_cu(N2, CHI);
-    const char* e = getenv("PQD_SPLIT");
-    const int mode = e ? atoi(e) : 1;
-    // more trunks than the device holds as co-resident groups: consecutive launches of as many as fit (C5 tomography:
-    // 8 six-level trunks = 288 workgroups on 256 CUs -> 7 + 1; a group steps ~7x faster than a batched block)
-    const int fit = bpc >= 1 ? (n_cu * bpc) / split_group_size(N2) : 0;
-    P->tk_chunk = fit >= 1 && nt > fit ? fit : 0;
-    P->tk_split = mode != 0 && N2 >= 9 && bpc >= 1 && fit >= 1 &&
-                  split_supported(N2, CHI, std::min(nt, fit), n_cu * bpc) &&
-                  nt <= (N2 >= 25 ? 4 : 2) * fit;  // launches in a row still beat one batched pass (§4.6 latencies)
+    // more trunks than the device holds as co-resident groups: consecutive launches of as many as fit
+    const SplitCap cap = split_capacity(N2, CHI, env.split_ow, caps);
+    P->tk_chunk = cap.fit >= 1 && nt > cap.fit ? cap.fit : 0;
+    P->tk_split = env.split != 0 && N2 >= 9 && cap.takes(N2, CHI, nt, cap.launches, env.split_ow);
     HIPCHK(P->tk_Xs.alloc((size_t)nt * 4 * N2 * CHI));  // split exchange: 2 slots of granules (pt_split.hip)
     HIPCHK(P->tk_cnt.alloc((size_t)nt * 64));  // split arrival flags: two 128-B lines per group
     HIPCHK(P->tk_err.alloc(4));
-    (void)ctx;
     return PQD_OK;
 }
 
@@ -639,9 +720,8 @@ static int plan_trunks(pqd_plan* P, pqd_ctx* ctx, int n_sys, const std::vector<s
 // N2 = 16, chi = 64, BT = 8, 3M unit-list PT rows with at most two units per wave (umax counts the list's end
 // marker too), 3M columns, fused half steps, traces one lane per (trajectory, output, row), no ablation. Every other
 // plan runs the general instance. PQD_SWEEP_LEAN=0 forces the general instance (A/B, tests).
-static bool sweep_lean_ok(const pqd_plan* P, const SweepParams& sp) {
-    if (const char* e = getenv("PQD_SWEEP_LEAN"); e && atoi(e) == 0) return false;
-    return P->N2 == 16 && P->CHI == 64 && P->BT == 8 && sp.pt_mode == 4 && sp.cmul3 == 1 && sp.fuse == 1 &&
+static bool sweep_lean_ok(const pqd_plan* P, const SweepParams& sp, const PlanEnv& env) {
+    return env.sweep_lean && P->N2 == 16 && P->CHI == 64 && P->BT == 8 && sp.pt_mode == 4 && sp.cmul3 == 1 && sp.fuse == 1 &&
            sp.trpre == 1 && sp.ablate == 0 && sp.units && sp.umax >= 2 && sp.umax <= 3 &&
            P->BT * sp.n_out * P->N2 <= 512;
 }
@@ -677,10 +757,12 @@ static hipError_t launch_trunks(pqd_plan* P, hipStream_t s) {
     return launch_sweep(P->N2, P->CHI, P->tk_BT, P->tk_blocks, P->tk, s);
 }
 
-int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const int32_t* traj_sys,
-                          const pqd_grid* grid, const pqd_pt* pt, const int32_t* sched, const pqd_c128* rho0,
-                          int32_t n_out, const pqd_c128* out_ops, const pqd_traj* tr, int64_t out_len,
-                          pqd_plan** out) {
+// ---- plan creation, stage by stage, in the order pqd_plan_create_multi calls them; values pass as arguments and results
+// the arguments of pqd_plan_create_multi; sch: the slice of every step (sched, or the PT's own order)
+static int check_plan_args(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const int32_t* traj_sys,
+                           const pqd_grid* grid, const pqd_pt* pt, const int32_t* sched, const pqd_c128* rho0,
+                           int32_t n_out, const pqd_c128* out_ops, const pqd_traj* tr, int64_t out_len,
+                           pqd_plan** out, std::vector<int32_t>& sch) {
     if (!ctx || !rho0 || !tr || !out || !systems) return fail(PQD_ERR_ARG, "NULL argument");
     if (n_sys < 1) return fail(PQD_ERR_ARG, "n_sys must be >= 1");
     if (n_sys > 1 && !traj_sys) return fail(PQD_ERR_ARG, "traj_sys is NULL with n_sys > 1");
@@ -694,7 +776,6 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
         if (traj_sys && (traj_sys[t] < 0 || traj_sys[t] >= n_sys)) return fail(PQD_ERR_ARG, "traj_sys[%d]=%d out of [0,%d)", t, traj_sys[t], n_sys);
     if ((rc = check_grid(grid))) return rc;
     const int N = sys->dim, N2 = N * N;
-    const size_t m2 = (size_t)N2 * N2;
     const int ns = grid->n_steps;
     if (n_out < 1 || n_out > 256 || !out_ops) return fail(PQD_ERR_ARG, "n_out %d not in [1, 256]", n_out);
     if (tr->n_traj < 0 || (tr->n_traj > 0 && (!tr->out_begin || !tr->out_end || !tr->out_offset)))
@@ -721,7 +802,7 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
         if (tr->mto_step[q] < 0 || tr->mto_step[q] > ns) return fail(PQD_ERR_ARG, "MTO %d: step %d outside [0, %d]", q, tr->mto_step[q], ns);
         if (tr->mto_kind[q] < 0 || tr->mto_kind[q] > 2) return fail(PQD_ERR_ARG, "MTO %d: kind %d", q, tr->mto_kind[q]);
     }
-    std::vector<int32_t> sch(std::max(1, ns), 0);
+    sch.assign(std::max(1, ns), 0);
     if (pt) {
         for (int n = 0; n < ns; ++n) {
             const int s = sched ? sched[n] : std::min(n, pt->n_slices - 1);
@@ -729,37 +810,28 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
             sch[n] = s;
         }
     }
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    auto* P = new pqd_plan;
-    std::unique_ptr<pqd_plan> guard(P);
-    P->ctx = ctx; P->N2 = N2; P->n_traj = tr->n_traj; P->n_steps = ns; P->out_len = out_len;
-    P->n_out = n_out; P->t_start = grid->ta; P->dt = grid->dt;
-    P->toff.assign(tr->n_traj + 1, 0);
-    for (int t = 0; t < tr->n_traj; ++t)
-        P->toff[t + 1] = P->toff[t] + (long long)(1 + n_out) * (tr->out_end[t] - tr->out_begin[t] + 1);
-    P->nopt = (pt == nullptr);
-    P->CHI = pt ? pt->CHI : 1;
-    P->n_sys = n_sys;
+    return PQD_OK;
+}
 
-    // ---- generators for the free propagators (one table entry per system)
-    if ((rc = upload_systems(n_sys, systems, s, P->L0, P->S, P->T, P->samples, P->systab))) return rc;
-    HIPCHK(P->M.alloc(std::max<size_t>(1, (size_t)n_sys * 2 * ns * m2)));
-    std::vector<int> tsys(std::max(1, tr->n_traj), 0);
-    for (int t = 0; t < tr->n_traj; ++t) tsys[t] = traj_sys ? traj_sys[t] : 0;
-    HIPCHK(P->traj_sys.upload(tsys.data(), tsys.size(), s));
-
-    // ---- MTO events: per trajectory, stable-sorted by (step, phase), same-slot ops composed. Every MTO kind is
-    // rho -> L rho R ("": A rho A^dag, _left: A rho, _right: rho A), so a slot's ops compose as N x N products
-    // (L = L_k ... L_1, R = R_1 ... R_k) and its superoperator is L (x) R^T; identical (L, R) pairs share one
-    // superoperator (a two-time sweep applies the same operators at every t1).
-    std::vector<std::vector<int>> per(tr->n_traj);
-    for (int q = 0; q < tr->n_mto; ++q) per[tr->mto_traj[q]].push_back(q);
-    std::vector<int> ev_start(tr->n_traj + 1, 0);
+// MTO events: per trajectory (events ev_start[t] .. ev_start[t + 1]), stable-sorted by (step, phase), same-slot ops
+// composed: evs = (step, 1 after the output / 0 before, superoperator index, 0). Every MTO kind is
+// rho -> L rho R ("": A rho A^dag, _left: A rho, _right: rho A), so a slot's ops compose as N x N products
+// (L = L_k ... L_1, R = R_1 ... R_k) and its superoperator is L (x) R^T; identical (L, R) pairs share one
+// superoperator (a two-time sweep applies the same operators at every t1).
+struct MtoEvents {
+    std::vector<int> ev_start;
     std::vector<int4> evs;
     std::vector<cd> sops;
+};
+static MtoEvents compose_mtos(int N, const pqd_traj* tr) {
+    const int N2 = N * N;
+    const size_t m2 = (size_t)N2 * N2, nn = (size_t)N * N;
+    std::vector<std::vector<int>> per(tr->n_traj);
+    for (int q = 0; q < tr->n_mto; ++q) per[tr->mto_traj[q]].push_back(q);
+    MtoEvents E;
+    auto &ev_start = E.ev_start; auto &evs = E.evs; auto &sops = E.sops;
+    ev_start.assign(tr->n_traj + 1, 0);
     std::unordered_map<std::string, int> sop_index;
-    const size_t nn = (size_t)N * N;
     std::vector<cd> Lm(nn), Rm(nn), Lq(nn), Rq(nn), key_buf(2 * nn);
     auto eye = [&](std::vector<cd>& M) { std::fill(M.begin(), M.end(), cd(0)); for (int i = 0; i < N; ++i) M[(size_t)i * N + i] = 1.0; };
     for (int t = 0; t < tr->n_traj; ++t) {
@@ -809,290 +881,339 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
     ev_start[tr->n_traj] = (int)evs.size();
     if (evs.empty()) evs.push_back(make_int4(-1, -1, 0, 0));
     if (sops.empty()) sops.assign(m2, 0.0);
-    HIPCHK(P->ev.upload(evs.data(), evs.size(), s));
-    HIPCHK(P->ev_start.upload(ev_start.data(), ev_start.size(), s));
-    HIPCHK(P->sop.upload(reinterpret_cast<double2*>(sops.data()), sops.size(), s));
+    return E;
+}
 
-    // ---- output operators: ovec[k][i*N+j] = O_k[j][i]   (<O> = Tr(O rho))
+// the plan's inputs on the device: generators for the free propagators (one table entry per system), MTO events,
+// output operators (ovec[k][i*N+j] = O_k[j][i], <O> = Tr(O rho)), initial state, windows
+static int upload_inputs(pqd_plan* P, const pqd_system* systems, const std::vector<int>& tsys, MtoEvents& E,
+                         const pqd_c128* rho0, const pqd_c128* out_ops, const pqd_traj* tr, hipStream_t s) {
+    const int N = systems->dim, N2 = P->N2, n_out = P->n_out, n_w = std::max(1, P->n_traj);
+    int rc = upload_systems(P->n_sys, systems, s, P->L0, P->S, P->T, P->samples, P->systab);
+    if (rc) return rc;
+    HIPCHK(P->M.alloc(std::max<size_t>(1, (size_t)P->n_sys * 2 * P->n_steps * N2 * N2)));
+    HIPCHK(P->traj_sys.upload(tsys.data(), tsys.size(), s));
+    HIPCHK(P->ev.upload(E.evs.data(), E.evs.size(), s));
+    HIPCHK(P->ev_start.upload(E.ev_start.data(), E.ev_start.size(), s));
+    HIPCHK(P->sop.upload(reinterpret_cast<double2*>(E.sops.data()), E.sops.size(), s));
     std::vector<cd> ov((size_t)n_out * N2);
     for (int k = 0; k < n_out; ++k)
         for (int i = 0; i < N; ++i)
             for (int j = 0; j < N; ++j) ov[(size_t)k * N2 + i * N + j] = C(out_ops)[(size_t)k * N2 + j * N + i];
     HIPCHK(P->ovec.upload(reinterpret_cast<double2*>(ov.data()), ov.size(), s));
     HIPCHK(P->rho0.upload(reinterpret_cast<const double2*>(rho0), N2, s));
+    HIPCHK(P->wbeg.upload(tr->out_begin, n_w, s));
+    HIPCHK(P->wend.upload(tr->out_end, n_w, s));
+    HIPCHK(P->woff.upload(reinterpret_cast<const long long*>(tr->out_offset), n_w, s));
+    return PQD_OK;
+}
 
-    // ---- trajectory windows and block grouping (longest first so lock-step blocks end together)
-    HIPCHK(P->wbeg.upload(tr->out_begin, std::max(1, tr->n_traj), s));
-    HIPCHK(P->wend.upload(tr->out_end, std::max(1, tr->n_traj), s));
-    HIPCHK(P->woff.upload(reinterpret_cast<const long long*>(tr->out_offset), std::max(1, tr->n_traj), s));
-    std::vector<int> order(tr->n_traj);
-    for (int t = 0; t < tr->n_traj; ++t) order[t] = t;
-    // j[t]: last step whose top still sees the MTO-free state (branch_slots)
-    std::vector<int> jv(std::max(1, tr->n_traj), 0);
+// Block order of the trajectories and j[t], the last step whose top still sees the MTO-free state (branch_slots):
+// grouped by system (a workgroup whose trajectories share one system reads one set of free propagators), longest
+// first inside a system so lock-step blocks end together, then by branch step (neighbouring slots share the longest
+// trunk)
+struct TrajOrder {
+    std::vector<int> order, jv;
+};
+static TrajOrder order_trajectories(const pqd_traj* tr, const std::vector<int>& tsys, const MtoEvents& E) {
+    TrajOrder o;
+    o.order.resize(tr->n_traj);
+    for (int t = 0; t < tr->n_traj; ++t) o.order[t] = t;
+    o.jv.assign(std::max(1, tr->n_traj), 0);
     for (int t = 0; t < tr->n_traj; ++t) {
-        if (ev_start[t] == ev_start[t + 1]) { jv[t] = tr->out_end[t]; continue; }
-        const int4 e = evs[ev_start[t]];
-        jv[t] = e.y == 1 ? e.x : e.x - 1;
+        if (E.ev_start[t] == E.ev_start[t + 1]) { o.jv[t] = tr->out_end[t]; continue; }
+        const int4 e = E.evs[E.ev_start[t]];
+        o.jv[t] = e.y == 1 ? e.x : e.x - 1;
     }
-    // group by system (a workgroup whose trajectories share one system reads one set of free propagators),
-    // longest first inside a system, then by branch step (neighbouring slots share the longest trunk)
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+    std::stable_sort(o.order.begin(), o.order.end(), [&](int a, int b) {
         if (tsys[a] != tsys[b]) return tsys[a] < tsys[b];
         if (tr->out_end[a] != tr->out_end[b]) return tr->out_end[a] > tr->out_end[b];
-        return jv[a] < jv[b];
+        return o.jv[a] < o.jv[b];
     });
-    // trajectories per workgroup: 8 (half the PT-slice L2 traffic per trajectory) when the LDS allows it
-    // and the batch still fills every CU, else 4
-    int n_cu = 256;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) n_cu = prop.multiProcessorCount;
-    }
+    return o;
+}
+// The kernel a plan runs and its grid (choose_path)
+struct PlanShape {
+    int N2, CHI, n_steps, n_out, n_sys;
+    bool pt;  // the plan has a process tensor
+};
+struct PathChoice {
+    bool split = false;    // small batch: one trajectory over N2 workgroups (pt_split.hip)
+    int split_chunk = 0;   // ... trajectories per launch when the batch exceeds the device (0: one launch)
+    int BT = 4;            // trajectories per lock-step workgroup
+    bool quad = false;     // two-level system: register-resident quads (pt_quad.hip), blocks of BT = 4
+    int qpw = 2, qcg = 4;  // ... quads per workgroup, 4-column groups per wave
+    bool msplit = false;   // split groups of ms_TB trajectories each (pt_msplit.hip)
+    int ms_TB = 0, ms_groups = 0, ms_xcd = 0;  // ... groups, groups per XCD slot (0: the plain grid)
+};
+
+// Path selection: single-trajectory split groups, else quads (N2 = 4), else multi-trajectory split groups, else the
+// batched sweep; a plan without PT takes none of them. Reads its arguments only: no plan, no HIP call beyond the
+// occupancy queries of `caps`. Fails for a chi = 256 batch the multi-trajectory groups cannot take.
+static int choose_path(const PlanShape& sh, const pqd_traj* tr, const std::vector<int>& tsys, const TrajOrder& to,
+                       const MtoEvents& E, const PlanEnv& env, const DeviceCaps& caps, PathChoice& pc) {
+    const int N2 = sh.N2, CHI = sh.CHI, n_traj = tr->n_traj, n_cu = caps.n_cu;
+    const bool fuse_on = sh.pt && sh.n_steps > 0 && env.fuse;
     // latency path: a batch whose trajectories fit one group of N2 workgroups each on the device runs
     // each trajectory over N2 workgroups (pt_split.hip). Measured: 2.3-3.6x faster per step
     // at N2 = 16 and 36; at N2 = 4 the batched kernel's single workgroup is as fast, so auto mode skips it.
     // PQD_SPLIT: 0 off, 1 auto, 2 whenever the device holds the groups.
-    {
-        const char* e = getenv("PQD_SPLIT");
-        const int mode = e ? atoi(e) : 1;
-        // the spin hand-off needs every workgroup of a group resident: the occupancy the runtime reports for the
-        // split kernel (one workgroup per CU by its LDS request) must cover all n_traj * N2 workgroups
-        const int bpc = (pt && mode != 0) ? split_blocks_per_cu(N2, P->CHI) : 0;
-        // a batch just above what the device holds runs as consecutive co-resident launches (up to 4 at N2 >= 25,
-        // 2 below: a group step is 3.6x / 2.4x faster than a batched block's)
-        const int fit = bpc >= 1 ? (n_cu * bpc) / split_group_size(N2) : 0;
-        // (not where multi-trajectory groups can take the batch: one launch of those beats consecutive launches)
-        const char* msa = getenv("PQD_MSPLIT");
-        const bool ms_can = !(msa && atoi(msa) == 0) && msplit_supported(N2, P->CHI, n_out) &&
-                            [] { const char* f = getenv("PQD_FUSE"); return f ? atoi(f) != 0 : true; }();
-        const int max_launches = ms_can ? 1 : (N2 >= 25 ? 4 : 2);
-        const char* ms = getenv("PQD_MSPLIT");  // 2: multi-trajectory split groups in place of these (A/B, tests)
-        P->split = pt && mode != 0 && !(ms && atoi(ms) == 2) && fit >= 1 && split_supported(N2, P->CHI, std::min(tr->n_traj, fit), n_cu * bpc) &&
-                   tr->n_traj <= max_launches * fit && (mode == 2 || N2 >= 9);
-        P->split_chunk = P->split && tr->n_traj > fit ? fit : 0;
+    if (sh.pt && env.split != 0) {
+        const SplitCap cap = split_capacity(N2, CHI, env.split_ow, caps);
+        // one launch only where multi-trajectory groups can take the batch (one launch of those beats consecutive
+        // launches). ms_can is a guess from PQD_MSPLIT, msplit_supported and PQD_FUSE alone: the decision below may
+        // still refuse the batch, which then runs batched
+        const bool ms_can = env.msplit != 0 && msplit_supported(N2, CHI, sh.n_out) && env.fuse;
+        // PQD_MSPLIT=2: multi-trajectory split groups in place of these (A/B, tests)
+        pc.split = env.msplit != 2 && cap.takes(N2, CHI, n_traj, ms_can ? 1 : cap.launches, env.split_ow) &&
+                   (env.split == 2 || N2 >= 9);
+        pc.split_chunk = pc.split && n_traj > cap.fit ? cap.fit : 0;
     }
-    int BT = (sweep_max_bt(N2) >= 8 && tr->n_traj >= 8 * n_cu) ? 8 : 4;
-    if (const char* e = getenv("PQD_BT")) BT = std::min(atoi(e) >= 8 ? 8 : 4, sweep_max_bt(N2));
-    if (P->CHI > 64) BT = 4;  // chi = 128: only four augmented states fit the LDS
+    // trajectories per workgroup: 8 (half the PT-slice L2 traffic per trajectory) when the LDS allows it
+    // and the batch still fills every CU, else 4
+    pc.BT = (sweep_max_bt(N2) >= 8 && n_traj >= 8 * n_cu) ? 8 : 4;
+    if (env.bt) pc.BT = std::min(env.bt, sweep_max_bt(N2));
+    if (CHI > 64) pc.BT = 4;  // chi = 128: only four augmented states fit the LDS
     // two-level system: the register-resident quad kernel (pt_quad.hip) unless split groups were forced or
-    // PQD_QUAD=0 (A/B); its blocks are quads
-    {
-        const char* e = getenv("PQD_QUAD");
-        // chi = 64 quads only on request (PQD_QUAD=2): their slices do not fit the registers yet and the batched
-        // kernel is faster (C2 shape at chi = 64: 19.9 ms batched, 41.9 ms quads; profiles/r03/q64.log)
-        P->quad = pt && !P->split && quad_supported(N2, P->CHI) && !(e && atoi(e) == 0) &&
-                  (P->CHI != 64 || (e && atoi(e) == 2));
-        // chi = 32: one quad per workgroup, so the two 8-column-strip workgroups sharing a CU barrier independently
-        // (C2: 19.8 -> 18.4 ms per launch with the strips below, profiles/r02/quad/envab_qpw_qcg.log)
-        if (P->CHI == 32) P->qpw = 1;
-        if (const char* w = getenv("PQD_QPW")) P->qpw = std::max(1, atoi(w));
-        if (P->quad) BT = 4;
+    // PQD_QUAD=0 (A/B); its blocks are quads.
+    // chi = 64 quads only on request (PQD_QUAD=2): their slices do not fit the registers yet and the batched
+    // kernel is faster (C2 shape at chi = 64: 19.9 ms batched, 41.9 ms quads; profiles/r03/q64.log)
+    pc.quad = sh.pt && !pc.split && quad_supported(N2, CHI) && env.quad != 0 && (CHI != 64 || env.quad == 2);
+    // chi = 32: one quad per workgroup, so the two 8-column-strip workgroups sharing a CU barrier independently
+    // (C2: 19.8 -> 18.4 ms per launch with the strips below, profiles/r02/quad/envab_qpw_qcg.log). Set whether or not
+    // the plan runs quads
+    if (CHI == 32) pc.qpw = 1;
+    if (env.qpw) pc.qpw = env.qpw;
+    if (pc.quad) {
+        pc.BT = 4;
+        // strips of 8 columns (twice the waves, two per SIMD) overlap one wave's round trips with the
+        // other's MFMAs: with no more quads than CUs (C2 single run 17.2 -> 13.1 ms), and at chi = 32 with one quad per
+        // workgroup on a full device too (C2 scan 18.9 -> 18.4 ms); chi = 16 full devices keep the 16-column strips.
+        // qpw is then set to the quads per workgroup launch_quad instantiates for (CHI, qcg), so that the trunk
+        // estimate and PQD_QPW mean what the kernel runs
+        const int nbq = (n_traj + pc.BT - 1) / pc.BT;  // blocks (build_blocks)
+        pc.qcg = (nbq <= n_cu || (CHI == 32 && pc.qpw == 1)) ? 2 : 4;
+        if (env.qcg) pc.qcg = (env.qcg == 1 && CHI != 32) ? 4 : env.qcg;
+        pc.qpw = quad_qpw(CHI, pc.qpw, pc.qcg);
     }
-    P->BT = BT;
-    std::vector<int> bt, be, bs, ba, bsrc;
-    {
-        const char* e = getenv("PQD_BRANCH");
-        P->branch = (e && atoi(e) == 0) ? 0 : 1;
-    }
-    const bool fuse_on = !P->nopt && ns > 0 && [] { const char* f = getenv("PQD_FUSE"); return f ? atoi(f) != 0 : true; }();
     // batches the single-trajectory split groups do not take: split groups of TB trajectories each (pt_msplit.hip),
     // G = N2 / 2 workgroups per group (N2 = 9: 9), up to 32 / G groups per XCD (their hand-offs in one L2). PQD_MSPLIT: 0 off, 1 auto,
     // 2 whenever supported; PQD_MS_TB forces the trajectories per group
-    int ms_groups = 0, ms_TB = 0, ms_xcd = 0;
-    {
-        const char* e = getenv("PQD_MSPLIT");
-        int mode = e ? atoi(e) : 1;
-        // PQD_SPLIT=0 (batched kernel only) and a forced trunk pre-pass (PQD_TRUNK=1) keep the batched path
-        if (const char* sp0 = getenv("PQD_SPLIT"); sp0 && atoi(sp0) == 0) mode = 0;
-        if (const char* tk = getenv("PQD_TRUNK"); tk && atoi(tk) == 1 && mode == 1) mode = 0;
-        if (pt && P->CHI == 256) mode = 2;  // no other path holds chi = 256
-        const int bpc = (pt && !P->split && mode != 0 && fuse_on && tr->n_traj >= 1 && msplit_supported(N2, P->CHI, n_out))
-                            ? msplit_blocks_per_cu(N2, P->CHI) : 0;
-        if (bpc >= 1) {
-            const int G = msplit_group_size(N2, P->CHI);
-            const int resident = n_cu * bpc / G;          // groups the device holds at once
-            const int gps = 32 / G;                        // groups per XCD slot (32 CUs per XCD on MI355X)
-            // PQD_SPLIT_XCD=0: the plain grid (groups may span XCDs, sc1 exchange), as many groups as are resident
-            bool xgrid = [] { const char* x = getenv("PQD_SPLIT_XCD"); return !(x && atoi(x) == 0); }();
-            // where the XCD slots hold fewer groups than the device (G > 16: one group of 18 per 32 CUs at N2 = 36)
-            // and that leaves more than 8 trajectories per group, the plain grid's extra groups pay for its cross-XCD
-            // exchange (six-level, 128 trajectories: 11.6 against 14.6 us per grid step; equal at 64, slower below,
-            // profiles/r06/msx2/)
-            if (xgrid && gps >= 1 && 8 * gps < resident) {
-                const int tbx = (tr->n_traj + 8 * gps - 1) / (8 * gps), tbp = (tr->n_traj + resident - 1) / resident;
-                if (tbx > 8 && tbp < tbx) xgrid = false;
+    int mode = env.msplit;
+    // PQD_SPLIT=0 (batched kernel only) and a forced trunk pre-pass (PQD_TRUNK=1) keep the batched path
+    if (env.split == 0) mode = 0;
+    if (env.trunk == 1 && mode == 1) mode = 0;
+    if (sh.pt && CHI == 256) mode = 2;  // no other path holds chi = 256
+    const int bpc = (sh.pt && !pc.split && mode != 0 && fuse_on && n_traj >= 1 && msplit_supported(N2, CHI, sh.n_out))
+                        ? caps.msplit_blocks_per_cu(N2, CHI) : 0;
+    if (bpc >= 1) {
+        const int G = msplit_group_size(N2, CHI);
+        const int resident = n_cu * bpc / G;          // groups the device holds at once
+        const int gps = 32 / G;                        // groups per XCD slot (32 CUs per XCD on MI355X)
+        // PQD_SPLIT_XCD=0: the plain grid (groups may span XCDs, sc1 exchange), as many groups as are resident
+        bool xgrid = env.split_xcd;
+        // where the XCD slots hold fewer groups than the device (G > 16: one group of 18 per 32 CUs at N2 = 36)
+        // and that leaves more than 8 trajectories per group, the plain grid's extra groups pay for its cross-XCD
+        // exchange (six-level, 128 trajectories: 11.6 against 14.6 us per grid step; equal at 64, slower below,
+        // profiles/r06/msx2/)
+        if (xgrid && gps >= 1 && 8 * gps < resident) {
+            const int tbx = (n_traj + 8 * gps - 1) / (8 * gps), tbp = (n_traj + resident - 1) / resident;
+            if (tbx > 8 && tbp < tbx) xgrid = false;
+        }
+        const int max_groups = std::min(resident, (xgrid && gps >= 1) ? 8 * gps : resident);
+        const int TB = std::max((n_traj + max_groups - 1) / std::max(1, max_groups), env.ms_tb);
+        const int n_groups = (n_traj + TB - 1) / TB;
+        // auto: while a group's per-step work stays below the batched kernel's per-step time
+        // (DESIGN.md §4.10); the single-trajectory groups keep the batches they fit
+        // and while shared trunks would save little: the batched sweep starts each slot at its branch step (a
+        // G2_reuse grid saves about half of its steps there), a split group runs every trajectory from step 0
+        // (a system's trunk itself is propagated once: what sharing saves is the activations beyond its longest)
+        int64_t shared = 0, total = 0;
+        std::vector<int> amax(sh.n_sys, 0);
+        for (int t = 0; t < n_traj; ++t) {
+            const int a = std::max(0, std::min(to.jv[t], tr->out_begin[t]));
+            shared += a;
+            amax[tsys[t]] = std::max(amax[tsys[t]], a);
+            total += tr->out_end[t] + 1;
+        }
+        for (int y = 0; y < sh.n_sys; ++y) shared -= amax[y];
+        // (measured, profiles/r06/bfly/c4ntraj.log, µs per grid step vs the batched kernel: 32 trajectories TB = 1
+        // 2.8 vs 13.5; 256 TB = 8 6.0 vs 11.8; 384 TB = 12 8.3 vs 11.5; 512 TB = 16 9.8 vs 11.1)
+        const bool want = mode == 2 || (TB <= 16 && 4 * shared <= total);
+        // a group's composite MTO steps are held in LDS (pt_msplit.hip s_cev): at most msplit_cev_max() per group
+        int max_cev = 0;
+        for (int k0 = 0; k0 < n_traj; k0 += TB) {
+            int c = 0;
+            for (int k = k0; k < std::min(n_traj, k0 + TB); ++k) {
+                const int t = to.order[k];
+                for (int i = E.ev_start[t]; i < E.ev_start[t + 1]; ++i)
+                    if (i == E.ev_start[t] || E.evs[i].x != E.evs[i - 1].x) ++c;
             }
-            const int max_groups = std::min(resident, (xgrid && gps >= 1) ? 8 * gps : resident);
-            int TB = (tr->n_traj + max_groups - 1) / std::max(1, max_groups);
-            if (const char* f = getenv("PQD_MS_TB")) TB = std::max(TB, atoi(f));
-            const int n_groups = (tr->n_traj + TB - 1) / TB;
-            // auto: while a group's per-step work stays below the batched kernel's per-step time
-            // (DESIGN.md §4.10); the single-trajectory groups keep the batches they fit
-            // and while shared trunks would save little: the batched sweep starts each slot at its branch step (a
-            // G2_reuse grid saves about half of its steps there), a split group runs every trajectory from step 0
-            // (a system's trunk itself is propagated once: what sharing saves is the activations beyond its longest)
-            int64_t shared = 0, total = 0;
-            std::vector<int> amax(n_sys, 0);
-            for (int t = 0; t < tr->n_traj; ++t) {
-                const int a = std::max(0, std::min(jv[t], tr->out_begin[t]));
-                shared += a;
-                amax[tsys[t]] = std::max(amax[tsys[t]], a);
-                total += tr->out_end[t] + 1;
-            }
-            for (int y = 0; y < n_sys; ++y) shared -= amax[y];
-            // (measured, profiles/r06/bfly/c4ntraj.log, µs per grid step vs the batched kernel: 32 trajectories TB = 1
-            // 2.8 vs 13.5; 256 TB = 8 6.0 vs 11.8; 384 TB = 12 8.3 vs 11.5; 512 TB = 16 9.8 vs 11.1)
-            const bool want = mode == 2 || (TB <= 16 && 4 * shared <= total);
-            // a group's composite MTO steps are held in LDS (pt_msplit.hip s_cev): at most msplit_cev_max() per group
-            int max_cev = 0;
-            for (int k0 = 0; k0 < tr->n_traj; k0 += TB) {
-                int c = 0;
-                for (int k = k0; k < std::min(tr->n_traj, k0 + TB); ++k) {
-                    const int t = order[k];
-                    for (int i = ev_start[t]; i < ev_start[t + 1]; ++i)
-                        if (i == ev_start[t] || evs[i].x != evs[i - 1].x) ++c;
-                }
-                max_cev = std::max(max_cev, c);
-            }
-            if (want && TB <= msplit_tbmax(N2, P->CHI) && n_groups <= resident && max_cev <= msplit_cev_max()) {
-                P->msplit = true;
-                ms_TB = TB;
-                ms_groups = n_groups;
-                ms_xcd = (xgrid && gps >= 1 && n_groups <= 8 * gps) ? (n_groups + 7) / 8 : 0;
-                if (const char* x = getenv("PQD_SPLIT_XCD"); x && atoi(x) == 0) ms_xcd = 0;
-            }
+            max_cev = std::max(max_cev, c);
+        }
+        if (want && TB <= msplit_tbmax(N2, CHI) && n_groups <= resident && max_cev <= msplit_cev_max()) {
+            pc.msplit = true;
+            pc.ms_TB = TB;
+            pc.ms_groups = n_groups;
+            pc.ms_xcd = (xgrid && gps >= 1 && n_groups <= 8 * gps) ? (n_groups + 7) / 8 : 0;
+            if (!env.split_xcd) pc.ms_xcd = 0;
         }
     }
-    if (pt && P->CHI == 256 && !P->msplit)
+    if (sh.pt && CHI == 256 && !pc.msplit)
         return fail(PQD_ERR_UNSUPPORTED, "chi 256 runs on multi-trajectory split groups only: %d trajectories at N2=%d do "
                     "not fit one launch of them (at most 8 per group), or the plan has no fused steps (PQD_FUSE=0)",
-                    tr->n_traj, N2);
-    const bool branch_on = P->branch != 0 && pt != nullptr && !P->split && !P->msplit;
-    // blocks are filled in this order and may straddle systems (each wave indexes its own system's propagators),
-    // so a scan with one trajectory per system still fills every slot of a workgroup
-    for (size_t k = 0; k < order.size();) {
-        const int sy = tsys[order[k]];
+                    n_traj, N2);
+    return PQD_OK;
+}
+
+// Lock-step blocks of BT slots, filled in block order. Blocks may straddle systems (each wave indexes its own
+// system's propagators), so a scan with one trajectory per system still fills every slot of a workgroup. bt: the
+// slots' trajectories (-1 empty), be / bs: a block's last step and first system, ba / bsrc: branch_slots
+struct Blocks {
+    std::vector<int> bt, be, bs, ba, bsrc;
+};
+static Blocks build_blocks(int BT, const TrajOrder& to, const std::vector<int>& tsys, const pqd_traj* tr,
+                           bool branch_on) {
+    Blocks B;
+    for (size_t k = 0; k < to.order.size();) {
+        const int sy = tsys[to.order[k]];
         int filled = 0, end = 0;
-        const size_t b0 = bt.size();
-        while (k < order.size() && filled < BT) {
-            bt.push_back(order[k]);
-            end = std::max(end, tr->out_end[order[k]]);
+        const size_t b0 = B.bt.size();
+        while (k < to.order.size() && filled < BT) {
+            B.bt.push_back(to.order[k]);
+            end = std::max(end, tr->out_end[to.order[k]]);
             ++k; ++filled;
         }
-        for (; filled < BT; ++filled) bt.push_back(-1);
+        for (; filled < BT; ++filled) B.bt.push_back(-1);
         // slots by branch step (empty ones last): the trunk passes from slot to slot
-        std::stable_sort(bt.begin() + b0, bt.end(), [&](int a, int b) {
+        std::stable_sort(B.bt.begin() + b0, B.bt.end(), [&](int a, int b) {
             if (a < 0 || b < 0) return a >= 0 && b < 0;
-            return jv[a] < jv[b];
+            return to.jv[a] < to.jv[b];
         });
-        ba.resize(bt.size());
-        bsrc.resize(bt.size());
-        branch_slots(BT, bt.data() + b0, jv, tr->out_begin, tsys, branch_on, ba.data() + b0, bsrc.data() + b0);
-        be.push_back(end);
-        bs.push_back(sy);
+        B.ba.resize(B.bt.size());
+        B.bsrc.resize(B.bt.size());
+        branch_slots(BT, B.bt.data() + b0, to.jv, tr->out_begin, tsys, branch_on, B.ba.data() + b0, B.bsrc.data() + b0);
+        B.be.push_back(end);
+        B.bs.push_back(sy);
     }
-    // quad kernel: strips of 8 columns (twice the waves, two per SIMD) overlap one wave's round trips with the
-    // other's MFMAs: with no more quads than CUs (C2 single run 17.2 -> 13.1 ms), and at chi = 32 with one quad per
-    // workgroup on a full device too (C2 scan 18.9 -> 18.4 ms); chi = 16 full devices keep the 16-column strips.
-    // P->qpw is then set to the quads per workgroup launch_quad instantiates for (CHI, qcg), so that the trunk
-    // estimate below and PQD_QPW mean what the kernel runs
-    if (P->quad) {
-        const int nbq = (int)be.size();
-        P->qcg = (nbq <= n_cu || (P->CHI == 32 && P->qpw == 1)) ? 2 : 4;
-        if (const char* e = getenv("PQD_QCG")) P->qcg = atoi(e) == 2 ? 2 : (atoi(e) == 1 && P->CHI == 32 ? 1 : 4);
-        P->qpw = quad_qpw(P->CHI, P->qpw, P->qcg);
-    }
-    // trunk pre-pass instead of in-workgroup chains: every slot starts at its own branch step from a checkpoint
-    // of its system's MTO-free trunk, which one trajectory per system propagates first. Chosen (PQD_TRUNK=-1,
-    // auto) when the estimated critical path — trunk latency + the longest block from its first activation — is
-    // shorter than the longest block from step 0; PQD_TRUNK=1 forces it, 0 disables it. Needs fused half steps
-    // (checkpoints hold the state with M_b(n-1) deferred).
-    std::vector<int> ca(bt.size(), 0);                 // per slot: activation with a checkpoint (0 = fresh)
-    std::vector<std::vector<int>> ck_steps(n_sys);     // per system: checkpoint steps (sorted, unique)
-    int trunk_mode = -1;
-    if (const char* e = getenv("PQD_TRUNK")) trunk_mode = atoi(e);
-    bool use_trunk = false;
-    if (branch_on && fuse_on && trunk_mode != 0 && ns > 0) {
-        // estimated main-sweep time in steps of one block: the longest block (critical path) or, with more blocks than
-        // the device holds at once, the total block-steps over the resident blocks, whichever is larger. Without the
-        // pre-pass a block spans [0, end] (its chain's first slot carries the trunk from step 0, dormant slots cost a
-        // lock-step block the same), with it [first activation, end]
-        int64_t crit_no = 0, crit_tk = 0, max_ck = 0, sum_no = 0, sum_tk = 0;
-        const int nbk = (int)be.size();
-        for (int b = 0; b < nbk; ++b) {
-            int start = INT_MAX;
-            for (int q = 0; q < BT; ++q) {
-                const int t = bt[(size_t)b * BT + q];
-                if (t < 0) continue;
-                const int a = std::max(0, std::min(jv[t], tr->out_begin[t]));
-                ca[(size_t)b * BT + q] = a;
-                start = std::min(start, a);
-                if (a >= 1) { ck_steps[tsys[t]].push_back(a); max_ck = std::max<int64_t>(max_ck, a); }
-            }
-            crit_no = std::max<int64_t>(crit_no, be[b]);
-            sum_no += be[b];
-            if (start != INT_MAX) {
-                crit_tk = std::max<int64_t>(crit_tk, be[b] - start);
-                sum_tk += be[b] - start;
-            }
-        }
-        // blocks resident at once: quads (one workgroup of qpw quads per CU) or BT-workgroups as the LDS allows
-        int64_t conc = n_cu;
-        if (P->quad) {
-            conc = (int64_t)n_cu * (P->CHI == 32 ? 2 : P->qpw);  // chi = 32: two quads per CU either way
-        } else {
-            const int64_t lds = ((int64_t)BT * (N2 * (P->CHI + 1) + 4) + (int64_t)BT * N2) * 16;
-            conc = (int64_t)n_cu * std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / std::max<int64_t>(1, lds)));
-        }
-        const double t_no = std::max((double)crit_no, (double)sum_no / (double)conc);
-        const double t_tk = std::max((double)crit_tk, (double)sum_tk / (double)conc);
-        // trunk step latency relative to a lock-step main-sweep step: split groups (N2 >= 9) ~0.5, one batched
-        // workgroup ~0.7
-        const double r = N2 >= 9 ? 0.5 : 0.7;
-        use_trunk = max_ck > 0 && (trunk_mode == 1 || t_tk + r * (double)max_ck < 0.995 * t_no);
-    }
-    if (use_trunk) {
-        std::vector<int> ck_base(n_sys, 0);
-        int n_ck = 0;
-        for (int y = 0; y < n_sys; ++y) {
-            auto& v = ck_steps[y];
-            std::sort(v.begin(), v.end());
-            v.erase(std::unique(v.begin(), v.end()), v.end());
-            ck_base[y] = n_ck;
-            n_ck += (int)v.size();
-        }
-        for (size_t i = 0; i < bt.size(); ++i) {
-            const int t = bt[i];
-            if (t < 0) continue;
-            const int a = ca[i];
-            if (a >= 1) {
-                const auto& v = ck_steps[tsys[t]];
-                const int idx = ck_base[tsys[t]] + (int)(std::lower_bound(v.begin(), v.end(), a) - v.begin());
-                ba[i] = a;
-                bsrc[i] = -2 - idx;
-            } else {
-                ba[i] = 0;
-                bsrc[i] = -1;
-            }
-        }
-        if ((rc = plan_trunks(P, ctx, n_sys, ck_steps, ck_base, n_ck, n_cu, N2, n_out, pt, s))) return rc;
-    }
-    for (size_t i = 0; i < bt.size(); ++i)
-        if (bt[i] >= 0) P->traj_steps += tr->out_end[bt[i]] - ba[i] + 1;
-    const int nb = (int)be.size();
-    if (bt.empty()) { bt.assign(BT, -1); be.assign(1, 0); bs.assign(1, 0); ba.assign(BT, INT_MAX); bsrc.assign(BT, -1); }
-    P->n_blocks = nb;
-    HIPCHK(P->blk_traj.upload(bt.data(), bt.size(), s));
-    HIPCHK(P->blk_end.upload(be.data(), be.size(), s));
-    HIPCHK(P->blk_sys.upload(bs.data(), bs.size(), s));
-    HIPCHK(P->blk_act.upload(ba.data(), ba.size(), s));
-    HIPCHK(P->blk_src.upload(bsrc.data(), bsrc.size(), s));
-    HIPCHK(P->sched.upload(sch.data(), sch.size(), s));
-    HIPCHK(P->out.alloc(std::max<int64_t>(1, out_len)));
-    HIPCHK(hipMemsetAsync(P->out.p, 0, std::max<int64_t>(1, out_len) * sizeof(double2), s));
+    return B;
+}
 
+// Trunk pre-pass instead of in-workgroup chains: every slot starts at its own branch step from a checkpoint
+// of its system's MTO-free trunk, which one trajectory per system propagates first. Chosen (PQD_TRUNK=-1,
+// auto) when the estimated critical path — trunk latency + the longest block from its first activation — is
+// shorter than the longest block from step 0; PQD_TRUNK=1 forces it, 0 disables it. Needs shared trunks (`enable`:
+// a batched or quad plan with PQD_BRANCH on) and fused half steps (checkpoints hold the state with M_b(n-1) deferred).
+struct TrunkChoice {
+    bool use_trunk = false;
+    std::vector<std::vector<int>> ck_steps;  // per system: checkpoint steps (as met; apply_trunks sorts them)
+    std::vector<int> ca;                     // per slot: activation with a checkpoint (0 = fresh)
+};
+static TrunkChoice choose_trunks(const PlanShape& sh, const PathChoice& pc, const Blocks& B, const TrajOrder& to,
+                                 const std::vector<int>& tsys, const pqd_traj* tr, bool enable, int trunk_mode,
+                                 int n_cu) {
+    TrunkChoice tc;
+    tc.ca.assign(B.bt.size(), 0);
+    tc.ck_steps.resize(sh.n_sys);
+    if (!enable || trunk_mode == 0 || sh.n_steps <= 0) return tc;
+    const int BT = pc.BT, N2 = sh.N2;
+    // estimated main-sweep time in steps of one block: the longest block (critical path) or, with more blocks than
+    // the device holds at once, the total block-steps over the resident blocks, whichever is larger. Without the
+    // pre-pass a block spans [0, end] (its chain's first slot carries the trunk from step 0, dormant slots cost a
+    // lock-step block the same), with it [first activation, end]
+    int64_t crit_no = 0, crit_tk = 0, max_ck = 0, sum_no = 0, sum_tk = 0;
+    const int nbk = (int)B.be.size();
+    for (int b = 0; b < nbk; ++b) {
+        int start = INT_MAX;
+        for (int q = 0; q < BT; ++q) {
+            const int t = B.bt[(size_t)b * BT + q];
+            if (t < 0) continue;
+            const int a = std::max(0, std::min(to.jv[t], tr->out_begin[t]));
+            tc.ca[(size_t)b * BT + q] = a;
+            start = std::min(start, a);
+            if (a >= 1) { tc.ck_steps[tsys[t]].push_back(a); max_ck = std::max<int64_t>(max_ck, a); }
+        }
+        crit_no = std::max<int64_t>(crit_no, B.be[b]);
+        sum_no += B.be[b];
+        if (start != INT_MAX) {
+            crit_tk = std::max<int64_t>(crit_tk, B.be[b] - start);
+            sum_tk += B.be[b] - start;
+        }
+    }
+    // blocks resident at once: quads (one workgroup of qpw quads per CU) or BT-workgroups as the LDS allows
+    int64_t conc = n_cu;
+    if (pc.quad) {
+        conc = (int64_t)n_cu * (sh.CHI == 32 ? 2 : pc.qpw);  // chi = 32: two quads per CU either way
+    } else {
+        const int64_t lds = ((int64_t)BT * (N2 * (sh.CHI + 1) + 4) + (int64_t)BT * N2) * 16;
+        conc = (int64_t)n_cu * std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / std::max<int64_t>(1, lds)));
+    }
+    const double t_no = std::max((double)crit_no, (double)sum_no / (double)conc);
+    const double t_tk = std::max((double)crit_tk, (double)sum_tk / (double)conc);
+    // trunk step latency relative to a lock-step main-sweep step: split groups (N2 >= 9) ~0.5, one batched
+    // workgroup ~0.7
+    const double r = N2 >= 9 ? 0.5 : 0.7;
+    tc.use_trunk = max_ck > 0 && (trunk_mode == 1 || t_tk + r * (double)max_ck < 0.995 * t_no);
+    return tc;
+}
+
+// the chosen trunk pre-pass: number the checkpoints, point every slot with an activation at its checkpoint (blk_src =
+// -2 - index) and lay the trunks out (plan_trunks)
+static int apply_trunks(pqd_plan* P, TrunkChoice& tc, Blocks& B, const std::vector<int>& tsys, const pqd_pt* pt,
+                        const PlanEnv& env, const DeviceCaps& caps, hipStream_t s) {
+    std::vector<int> ck_base(P->n_sys, 0);
+    int n_ck = 0;
+    for (int y = 0; y < P->n_sys; ++y) {
+        auto& v = tc.ck_steps[y];
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+        ck_base[y] = n_ck;
+        n_ck += (int)v.size();
+    }
+    for (size_t i = 0; i < B.bt.size(); ++i) {
+        const int t = B.bt[i];
+        if (t < 0) continue;
+        const int a = tc.ca[i];
+        if (a >= 1) {
+            const auto& v = tc.ck_steps[tsys[t]];
+            const int idx = ck_base[tsys[t]] + (int)(std::lower_bound(v.begin(), v.end(), a) - v.begin());
+            B.ba[i] = a;
+            B.bsrc[i] = -2 - idx;
+        } else {
+            B.ba[i] = 0;
+            B.bsrc[i] = -1;
+        }
+    }
+    return plan_trunks(P, tc.ck_steps, ck_base, n_ck, pt, env, caps, s);
+}
+
+// the blocks on the device (a plan without trajectories gets one empty block), their hash, and the trajectory-steps
+// of the main sweep (after the trunks' own, which plan_trunks counted); then the slice schedule and the output buffer.
+// Device buffers are allocated in the order plan creation always did: the sweep's time moves by up to 0.4% with where
+// its buffers lie (profiles/r08/plan_stages/), so the stages change nothing about their placement
+static int upload_blocks(pqd_plan* P, Blocks& B, const pqd_traj* tr, const std::vector<int32_t>& sch, hipStream_t s) {
+    for (size_t i = 0; i < B.bt.size(); ++i)
+        if (B.bt[i] >= 0) P->traj_steps += tr->out_end[B.bt[i]] - B.ba[i] + 1;
+    P->n_blocks = (int)B.be.size();
+    if (B.bt.empty()) { B.bt.assign(P->BT, -1); B.be.assign(1, 0); B.bs.assign(1, 0); B.ba.assign(P->BT, INT_MAX); B.bsrc.assign(P->BT, -1); }
+    HIPCHK(P->blk_traj.upload(B.bt.data(), B.bt.size(), s));
+    HIPCHK(P->blk_end.upload(B.be.data(), B.be.size(), s));
+    HIPCHK(P->blk_sys.upload(B.bs.data(), B.bs.size(), s));
+    HIPCHK(P->blk_act.upload(B.ba.data(), B.ba.size(), s));
+    HIPCHK(P->blk_src.upload(B.bsrc.data(), B.bsrc.size(), s));
+    P->h_blocks = fnv1a(B.bsrc, fnv1a(B.ba, fnv1a(B.bs, fnv1a(B.be, fnv1a(B.bt)))));
+    HIPCHK(P->sched.upload(sch.data(), sch.size(), s));
+    HIPCHK(P->out.alloc(std::max<int64_t>(1, P->out_len)));
+    HIPCHK(hipMemsetAsync(P->out.p, 0, std::max<int64_t>(1, P->out_len) * sizeof(double2), s));
+    return PQD_OK;
+}
+
+// the free-propagator build of a plan: idle operators and pulse windows. After the trunks: windows need n_trunk == 0
+static int setup_free_props(pqd_plan* P, const pqd_grid* grid, const PlanEnv& env, hipStream_t s) {
+    const int n_sys = P->n_sys, ns = P->n_steps;
+    const size_t m2 = (size_t)P->N2 * P->N2;
     P->fp.systems = P->systab.p; P->fp.n_sys = n_sys;
-    if (const char* ie = getenv("PQD_IDLE"); !(ie && atoi(ie) == 0)) {  // PQD_IDLE=0: compute every half step (A/B)
+    if (env.idle) {  // PQD_IDLE=0: compute every half step (A/B)
         HIPCHK(P->Midle.alloc((size_t)n_sys * m2));
         P->fp.Midle = P->Midle.p;
         // pulse windows: half steps outside a system's [first, last] non-idle half step are neither stored nor
@@ -1101,10 +1222,10 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
         // Windows only where every kernel of the plan reads through them: the quad and no-PT kernels without a
         // trunk pre-pass (the batched sweep reads every half step as stored; the split path may fall back to it).
         const bool win_ok = (P->nopt || P->quad) && P->n_trunk == 0;
-        if (const char* we = getenv("PQD_WIN"); win_ok && !(we && atoi(we) == 0)) {
+        if (win_ok && env.win != 0) {
             HIPCHK(P->win.alloc((size_t)n_sys));
             P->fp.win = P->win.p;
-            P->win_mode = we ? atoi(we) : 1;
+            P->win_mode = env.win;
         }
     }
     P->fp.ta = grid->ta; P->fp.dt = grid->dt; P->fp.n_steps = ns; P->fp.n_sub = grid->n_sub; P->fp.M = P->M.p;
@@ -1120,7 +1241,16 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
             P->fp.win = nullptr;
         }
     }
+    P->fp.packed4 = env.fp4;
+    P->fp.mfma = env.fpm;
+    return PQD_OK;
+}
 
+// the launch parameters of the main sweep: the plan's buffers, the kernel variants, the PT row units, the fused
+// half steps, and whether the plan runs the lean instance
+static int fill_sweep_params(pqd_plan* P, const pqd_pt* pt, const PlanEnv& env, hipStream_t s) {
+    const int n_sys = P->n_sys, ns = P->n_steps, N2 = P->N2, n_out = P->n_out;
+    const size_t m2 = (size_t)N2 * N2;
     SweepParams& sp = P->sp;
     sp.M = P->M.p;
     if (pt) {
@@ -1131,37 +1261,36 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
     sp.blk_traj = P->blk_traj.p; sp.blk_end = P->blk_end.p; sp.blk_sys = P->blk_sys.p;
     sp.blk_act = P->blk_act.p; sp.blk_src = P->blk_src.p;
     sp.traj_sys = P->traj_sys.p; sp.m_stride = (long long)2 * ns * m2; sp.wbeg = P->wbeg.p; sp.wend = P->wend.p;
-    { const char* ab = getenv("PQD_ABLATE"); sp.ablate = ab ? atoi(ab) : 0; }
+    sp.ablate = env.ablate;
     // exchange form: counter (default; with the XCD-grouped grid C3 runs 5.02 us per step against 5.33 for the granules,
     // profiles/r04/split/xcd/) or data-tagged granules (PQD_SPLIT_GRAN=1)
-    { const char* b1 = getenv("PQD_SPLIT_GRAN"); sp.split_gran = (b1 && atoi(b1) == 1) ? 1 : 0; }
-    sp.split_ow = split_ow_env() ? 1 : 0;  // the output workgroup (pt_split.hip OWG); split_group_size agrees
-    { const char* b2 = getenv("PQD_SPLIT_XCD"); sp.split_xcd = (b2 && atoi(b2) == 0) ? 0 : 1; }
-    { const char* b3 = getenv("PQD_SPLIT_L2"); sp.split_l2 = (b3 && atoi(b3) == 0) ? 0 : 1; }
+    sp.split_gran = env.split_gran ? 1 : 0;
+    sp.split_ow = env.split_ow ? 1 : 0;  // the output workgroup (pt_split.hip OWG): the flag split_capacity sized groups with
+    sp.split_xcd = env.split_xcd ? 1 : 0;
+    sp.split_l2 = env.split_l2 ? 1 : 0;
     // polls of a split group's counter before the wait counts as a timeout (~0.1 s); PQD_SPLIT_SPIN overrides
     // it (tests provoke the batched fallback with 0)
-    { const char* sl = getenv("PQD_SPLIT_SPIN"); sp.spin_limit = sl ? (unsigned)strtoul(sl, nullptr, 10) : (1u << 22); }
-    { const char* f4 = getenv("PQD_FP4"); P->fp.packed4 = (f4 && atoi(f4) == 0) ? 0 : 1; }
-    { const char* fm = getenv("PQD_FPM"); P->fp.mfma = fm ? atoi(fm) : 1; }
+    sp.spin_limit = env.split_spin;
     HIPCHK(P->flags.alloc(4));
     HIPCHK(hipMemsetAsync(P->flags.p, 0, 4 * sizeof(unsigned), s));
     sp.flags = P->flags.p;
     // PT rows: 3M on the matrix cores; at BT = 4 (N2 > 16, chi = 128) with two k-steps of the slice in flight
     // (six-level scan c5: 84.7 -> 79.5 ms per launch, profiles/r03/exp_c/c5_ptmode.log)
-    { const char* pm = getenv("PQD_PT_MODE"); sp.pt_mode = pm ? atoi(pm) : (P->BT == 4 ? 5 : 4); }
-    { const char* c3 = getenv("PQD_CMUL3"); sp.cmul3 = c3 ? atoi(c3) : 1; }
-    { const char* tp = getenv("PQD_TRPRE"); sp.trpre = tp ? atoi(tp) : 1; }
-    { const char* cb = getenv("PQD_COLBIG"); sp.colbig = cb ? atoi(cb) : 1; }
+    sp.pt_mode = env.pt_mode_set ? env.pt_mode : (P->BT == 4 ? 5 : 4);
+    sp.cmul3 = env.cmul3;
+    sp.trpre = env.trpre;
+    sp.colbig = env.colbig;
     if (pt && (sp.pt_mode == 4 || sp.pt_mode == 5)) {
         const int nw = P->BT * sweep_wpt(P->N2, P->BT, P->CHI);
         int rmax = sweep_rmax(P->N2, P->BT, P->CHI);
-        if (const char* e = getenv("PQD_ROWPAIR")) rmax = std::max(1, std::min(rmax, atoi(e) ? rmax : 1));
-        std::vector<int4> u = pt_row_units(pt->gmap_h, nw, rmax);
+        if (env.rowpair >= 0) rmax = std::max(1, std::min(rmax, env.rowpair ? rmax : 1));
+        std::vector<int4> u = pt_row_units(pt->gmap_h, nw, rmax, env.unitbal);
         HIPCHK(P->units.upload(u.data(), u.size(), s));
+        P->h_units = fnv1a(u);
         sp.units = P->units.p;
         sp.umax = (int)(u.size() / nw);
     }
-    { const char* fz = getenv("PQD_FUSE"); sp.fuse = (!P->nopt && ns > 0 && (fz ? atoi(fz) : 1)) ? 1 : 0; }
+    sp.fuse = (!P->nopt && ns > 0 && env.fuse) ? 1 : 0;
     if (!sp.fuse) sp.trpre = 0;  // the prefetched rows are W(n), which exists only with fused half steps
     if (sp.fuse) {
         HIPCHK(P->F.alloc((size_t)n_sys * ns * m2));
@@ -1180,62 +1309,117 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
     sp.win = P->win.p; sp.Midle = P->Midle.p; sp.Fidle = P->Fidle.p; sp.Widle = P->Widle.p;
     sp.woff = P->woff.p; sp.ev_start = P->ev_start.p; sp.ev = P->ev.p; sp.sop = P->sop.p; sp.out = P->out.p;
     sp.n_steps = ns;
-    sp.n_blk = nb;
+    sp.n_blk = P->n_blocks;
     // quad kernel: waves raise their priority outside the PT contraction, so a wave on its serial chain (column
     // operator, exchange, relayout) issues ahead of the other quad's MFMA stream on the same SIMD (C2: 17.5 -> 16.1 ms;
     // a static bias between the grid halves gains nothing; profiles/r03/quad_prio.log)
-    sp.qprio = 2;
-    if (const char* e = getenv("PQD_QPRIO")) sp.qprio = atoi(e) & 3;
-    sp.lean = sweep_lean_ok(P, sp) ? 1 : 0;
-    finalize_trunks(P);
-    if (P->split) {
-        HIPCHK(P->Xs.alloc((size_t)P->n_traj * 4 * N2 * P->CHI));  // split exchange: 2 slots of granules
-        HIPCHK(P->cnt.alloc((size_t)P->n_traj * 64));  // split arrival flags: two 128-B lines per group
-        HIPCHK(P->err.alloc(4));
+    sp.qprio = env.qprio;
+    sp.lean = sweep_lean_ok(P, sp, env) ? 1 : 0;
+    return PQD_OK;
+}
+
+// the tables and buffers of a plan on multi-trajectory split groups: the groups (consecutive trajectories of the
+// block order, ms_TB per group), the composite MTO events, the exchange and the launch parameters
+static int build_msplit_tables(pqd_plan* P, const PathChoice& pc, const std::vector<int>& order, const pqd_traj* tr,
+                               const std::vector<int>& tsys, const MtoEvents& E, const PlanEnv& env, hipStream_t s) {
+    const int ms_TB = pc.ms_TB, ms_groups = pc.ms_groups, ms_xcd = pc.ms_xcd, N2 = P->N2, n_out = P->n_out;
+    const size_t m2 = (size_t)N2 * N2;
+    std::vector<int> gt((size_t)ms_groups * ms_TB, -1), ge(ms_groups, 0);
+    for (int k = 0; k < tr->n_traj; ++k) {
+        const int gi = k / ms_TB, t = order[k];
+        gt[(size_t)gi * ms_TB + k % ms_TB] = t;
+        ge[gi] = std::max(ge[gi], tr->out_end[t]);
     }
-    if (P->msplit) {
-        // groups: consecutive trajectories of the block order (system, longest first), TB per group
-        std::vector<int> gt((size_t)ms_groups * ms_TB, -1), ge(ms_groups, 0);
-        for (int k = 0; k < tr->n_traj; ++k) {
-            const int gi = k / ms_TB, t = order[k];
-            gt[(size_t)gi * ms_TB + k % ms_TB] = t;
-            ge[gi] = std::max(ge[gi], tr->out_end[t]);
-        }
-        // composite MTO events: one per (trajectory, step) with MTOs, the before / after superoperators of that step
-        std::vector<int4> ce;
-        std::vector<int> cs(tr->n_traj + 1, 0);
-        for (int t = 0; t < tr->n_traj; ++t) {
-            cs[t] = (int)ce.size();
-            for (int i = ev_start[t]; i < ev_start[t + 1]; ++i) {
-                const int4 v = evs[i];
-                if (ce.size() > (size_t)cs[t] && ce.back().x == v.x) {
-                    if (v.y == 0) ce.back().y = v.z; else ce.back().z = v.z;
-                } else {
-                    ce.push_back(make_int4(v.x, v.y == 0 ? v.z : -1, v.y == 0 ? -1 : v.z, tsys[t]));
-                }
+    // composite MTO events: one per (trajectory, step) with MTOs, the before / after superoperators of that step
+    std::vector<int4> ce;
+    std::vector<int> cs(tr->n_traj + 1, 0);
+    for (int t = 0; t < tr->n_traj; ++t) {
+        cs[t] = (int)ce.size();
+        for (int i = E.ev_start[t]; i < E.ev_start[t + 1]; ++i) {
+            const int4 v = E.evs[i];
+            if (ce.size() > (size_t)cs[t] && ce.back().x == v.x) {
+                if (v.y == 0) ce.back().y = v.z; else ce.back().z = v.z;
+            } else {
+                ce.push_back(make_int4(v.x, v.y == 0 ? v.z : -1, v.y == 0 ? -1 : v.z, tsys[t]));
             }
         }
-        cs[tr->n_traj] = (int)ce.size();
-        P->n_cev = (int)ce.size();
-        if (ce.empty()) ce.push_back(make_int4(INT_MAX, -1, -1, 0));
-        HIPCHK(P->ms_gtraj.upload(gt.data(), gt.size(), s));
-        HIPCHK(P->ms_gend.upload(ge.data(), ge.size(), s));
-        HIPCHK(P->cev.upload(ce.data(), ce.size(), s));
-        HIPCHK(P->cev_start.upload(cs.data(), cs.size(), s));
-        HIPCHK(P->Fev.alloc((size_t)std::max(1, P->n_cev) * m2));
-        HIPCHK(P->Wev.alloc((size_t)std::max(1, P->n_cev) * n_out * N2));
-        HIPCHK(P->msX.alloc((size_t)ms_groups * ms_TB * 2 * N2 * P->CHI));
-        HIPCHK(P->ms_cnt.alloc((size_t)ms_groups * 64));
-        HIPCHK(P->err.alloc(4));
-        // L2-kept exchange lines on the XCD-grouped grid (PQD_MS_L2=0: sc1 stores, as on the plain grid)
-        const int l2keep = ms_xcd > 0 && [] { const char* f = getenv("PQD_MS_L2"); return f ? atoi(f) != 0 : true; }();
-        // PT contraction on the matrix cores from 3 trajectories per group (a row block of 4 rows per MFMA; below
-        // that the VALU path's per-trajectory work is smaller); PQD_MS_PTM=0/1 forces the VALU / matrix-core path
-        int ptm = ms_TB >= 3 && P->CHI <= 64;
-        if (const char* f = getenv("PQD_MS_PTM")) ptm = atoi(f) != 0;
-        P->mq = MsplitParams{P->ms_gtraj.p, P->ms_gend.p, P->cev_start.p, P->cev.p, P->Fev.p, P->Wev.p,
-                             ms_TB, ms_groups, ms_xcd, l2keep, ptm};
     }
+    cs[tr->n_traj] = (int)ce.size();
+    P->n_cev = (int)ce.size();
+    if (ce.empty()) ce.push_back(make_int4(INT_MAX, -1, -1, 0));
+    HIPCHK(P->ms_gtraj.upload(gt.data(), gt.size(), s));
+    HIPCHK(P->ms_gend.upload(ge.data(), ge.size(), s));
+    HIPCHK(P->cev.upload(ce.data(), ce.size(), s));
+    P->h_groups = fnv1a(ce, fnv1a(ge, fnv1a(gt)));
+    HIPCHK(P->cev_start.upload(cs.data(), cs.size(), s));
+    HIPCHK(P->Fev.alloc((size_t)std::max(1, P->n_cev) * m2));
+    HIPCHK(P->Wev.alloc((size_t)std::max(1, P->n_cev) * n_out * N2));
+    HIPCHK(P->msX.alloc((size_t)ms_groups * ms_TB * 2 * N2 * P->CHI));
+    HIPCHK(P->ms_cnt.alloc((size_t)ms_groups * 64));
+    HIPCHK(P->err.alloc(4));
+    // L2-kept exchange lines on the XCD-grouped grid (PQD_MS_L2=0: sc1 stores, as on the plain grid)
+    const int l2keep = ms_xcd > 0 && env.ms_l2;
+    // PT contraction on the matrix cores from 3 trajectories per group (a row block of 4 rows per MFMA; below
+    // that the VALU path's per-trajectory work is smaller); PQD_MS_PTM=0/1 forces the VALU / matrix-core path
+    const int ptm = env.ms_ptm >= 0 ? env.ms_ptm : (ms_TB >= 3 && P->CHI <= 64);
+    P->mq = MsplitParams{P->ms_gtraj.p, P->ms_gend.p, P->cev_start.p, P->cev.p, P->Fev.p, P->Wev.p,
+                         ms_TB, ms_groups, ms_xcd, l2keep, ptm};
+    return PQD_OK;
+}
+
+int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const int32_t* traj_sys,
+                          const pqd_grid* grid, const pqd_pt* pt, const int32_t* sched, const pqd_c128* rho0,
+                          int32_t n_out, const pqd_c128* out_ops, const pqd_traj* tr, int64_t out_len,
+                          pqd_plan** out) {
+    std::vector<int32_t> sch;
+    int rc = check_plan_args(ctx, n_sys, systems, traj_sys, grid, pt, sched, rho0, n_out, out_ops, tr, out_len, out, sch);
+    if (rc) return rc;
+    const PlanEnv env = read_plan_env();
+    const int N = systems->dim, N2 = N * N, ns = grid->n_steps, n_traj = tr->n_traj;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    auto* P = new pqd_plan;
+    std::unique_ptr<pqd_plan> guard(P);
+    P->ctx = ctx; P->N2 = N2; P->n_traj = n_traj; P->n_steps = ns; P->out_len = out_len;
+    P->n_out = n_out; P->t_start = grid->ta; P->dt = grid->dt;
+    P->toff.assign(n_traj + 1, 0);
+    for (int t = 0; t < n_traj; ++t)
+        P->toff[t + 1] = P->toff[t] + (long long)(1 + n_out) * (tr->out_end[t] - tr->out_begin[t] + 1);
+    P->nopt = (pt == nullptr);
+    P->CHI = pt ? pt->CHI : 1;
+    P->n_sys = n_sys;
+    DeviceCaps caps{256, split_blocks_per_cu, msplit_blocks_per_cu};
+    if (hipDeviceProp_t prop; hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) caps.n_cu = prop.multiProcessorCount;
+    P->n_cu = caps.n_cu;
+
+    std::vector<int> tsys(std::max(1, n_traj), 0);
+    for (int t = 0; t < n_traj; ++t) tsys[t] = traj_sys ? traj_sys[t] : 0;
+    MtoEvents E = compose_mtos(N, tr);
+    if ((rc = upload_inputs(P, systems, tsys, E, rho0, out_ops, tr, s))) return rc;
+
+    // decisions: block order, path, blocks, trunk pre-pass
+    const TrajOrder to = order_trajectories(tr, tsys, E);
+    const PlanShape sh{N2, P->CHI, ns, n_out, n_sys, pt != nullptr};
+    PathChoice pc;
+    if ((rc = choose_path(sh, tr, tsys, to, E, env, caps, pc))) return rc;
+    P->split = pc.split; P->split_chunk = pc.split_chunk; P->BT = pc.BT; P->quad = pc.quad; P->qpw = pc.qpw;
+    P->qcg = pc.qcg; P->msplit = pc.msplit; P->branch = env.branch ? 1 : 0;
+    const bool branch_on = env.branch && pt && !pc.split && !pc.msplit, fuse_on = pt && ns > 0 && env.fuse;
+    Blocks B = build_blocks(pc.BT, to, tsys, tr, branch_on);
+    TrunkChoice tc = choose_trunks(sh, pc, B, to, tsys, tr, branch_on && fuse_on, env.trunk, caps.n_cu);
+    if (tc.use_trunk && (rc = apply_trunks(P, tc, B, tsys, pt, env, caps, s))) return rc;
+    if ((rc = upload_blocks(P, B, tr, sch, s))) return rc;
+
+    // launch parameters
+    if ((rc = setup_free_props(P, grid, env, s))) return rc;
+    if ((rc = fill_sweep_params(P, pt, env, s))) return rc;
+    finalize_trunks(P);
+    if (pc.split) {
+        HIPCHK(P->Xs.alloc((size_t)n_traj * 4 * N2 * P->CHI));  // split exchange: 2 slots of granules
+        HIPCHK(P->cnt.alloc((size_t)n_traj * 64));  // split arrival flags: two 128-B lines per group
+        HIPCHK(P->err.alloc(4));
+    }
+    if (pc.msplit && (rc = build_msplit_tables(P, pc, to.order, tr, tsys, E, env, s))) return rc;
     HIPCHK(hipStreamSynchronize(s));
     *out = guard.release();
     return PQD_OK;
@@ -1395,14 +1579,20 @@ int pqd_plan_trapz(pqd_plan* P, int32_t n_pairs, const int32_t* k_head, const in
     return rc;
 }
 
+// the flat output length the trajectories' offsets and windows need
+static int64_t traj_out_len(const pqd_traj* tr, int32_t n_out) {
+    int64_t n = 0;
+    for (int t = 0; t < tr->n_traj; ++t)
+        n = std::max<int64_t>(n, tr->out_offset[t] + (int64_t)(tr->out_end[t] - tr->out_begin[t] + 1) * n_out);
+    return n;
+}
+
 int pqd_propagate_trapz(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const int32_t* traj_sys,
                         const pqd_grid* grid, const pqd_pt* pt, const int32_t* sched, const pqd_c128* rho0,
                         int32_t n_out, const pqd_c128* out_ops, const pqd_traj* tr, int32_t n_pairs,
                         const int32_t* k_head, const int32_t* k_tail, double dx, pqd_c128* res) {
     if (!tr) return fail(PQD_ERR_ARG, "NULL argument");
-    int64_t out_len = 0;
-    for (int t = 0; t < tr->n_traj; ++t)
-        out_len = std::max<int64_t>(out_len, tr->out_offset[t] + (int64_t)(tr->out_end[t] - tr->out_begin[t] + 1) * n_out);
+    const int64_t out_len = traj_out_len(tr, n_out);
     pqd_plan* P = nullptr;
     int rc = pqd_plan_create_multi(ctx, n_sys, systems, traj_sys, grid, pt, sched, rho0, n_out, out_ops, tr,
                                    std::max<int64_t>(1, out_len), &P);
@@ -1437,12 +1627,36 @@ int pqd_plan_sweep_lean(const pqd_plan* P, int32_t* on) {
     return PQD_OK;
 }
 
+static int plan_path(const pqd_plan* P) {
+    return P->nopt ? PQD_PATH_NOPT : P->split ? PQD_PATH_SPLIT : P->msplit ? PQD_PATH_MSPLIT
+         : P->quad ? PQD_PATH_QUAD : PQD_PATH_BATCHED;
+}
+
+int pqd_plan_describe(const pqd_plan* P, char* buf, int32_t len) {
+    if (!P || !buf || len < 1) return fail(PQD_ERR_ARG, "NULL argument");
+    const SweepParams& sp = P->sp;
+    const MsplitParams& mq = P->mq;
+    const int n = snprintf(
+        buf, (size_t)len,
+        "n_cu=%d path=%d BT=%d n_blocks=%d traj_steps=%lld split_chunk=%d quad=%d qpw=%d qcg=%d ms_TB=%d ms_groups=%d "
+        "ms_xcd=%d ms_l2keep=%d ms_ptm=%d n_cev=%d branch=%d n_trunk=%d tk_split=%d tk_chunk=%d tk_blocks=%d idle=%d "
+        "win=%d win_mode=%d fuse=%d pt_mode=%d cmul3=%d trpre=%d colbig=%d umax=%d tk_umax=%d lean=%d split_gran=%d "
+        "split_ow=%d split_xcd=%d split_l2=%d spin_limit=%u qprio=%d ablate=%d fp4=%d fpm=%d blocks=%016llx "
+        "units=%016llx groups=%016llx",
+        P->n_cu, plan_path(P), P->BT, P->n_blocks, (long long)P->traj_steps, P->split_chunk, P->quad ? 1 : 0, P->qpw,
+        P->qcg, mq.TB, mq.n_groups, mq.xcd, mq.l2keep, mq.ptm, P->n_cev, P->branch, P->n_trunk, P->tk_split ? 1 : 0,
+        P->tk_chunk, P->tk_blocks, P->fp.Midle ? 1 : 0, P->win.p ? 1 : 0, P->win_mode, sp.fuse, sp.pt_mode, sp.cmul3,
+        sp.trpre, sp.colbig, sp.umax, P->n_trunk ? P->tk.umax : 0, sp.lean, sp.split_gran, sp.split_ow, sp.split_xcd,
+        sp.split_l2, sp.spin_limit, sp.qprio, sp.ablate, P->fp.packed4, P->fp.mfma, (unsigned long long)P->h_blocks,
+        (unsigned long long)P->h_units, (unsigned long long)P->h_groups);
+    if (n < 0 || n >= len) return fail(PQD_ERR_ARG, "pqd_plan_describe: the line needs %d bytes, len is %d", n + 1, len);
+    return PQD_OK;
+}
+
 int pqd_plan_info(const pqd_plan* P, int32_t* path, int32_t* bt, int32_t* split_fallbacks, int64_t* traj_steps) {
     if (!P) return fail(PQD_ERR_ARG, "plan is NULL");
     if (traj_steps) *traj_steps = P->traj_steps;
-    if (path)
-        *path = P->nopt ? PQD_PATH_NOPT : P->split ? PQD_PATH_SPLIT : P->msplit ? PQD_PATH_MSPLIT
-              : P->quad ? PQD_PATH_QUAD : PQD_PATH_BATCHED;
+    if (path) *path = plan_path(P);
     if (bt) *bt = P->msplit ? P->mq.TB : P->BT;
     if (split_fallbacks) *split_fallbacks = P->split_fallbacks;
     return PQD_OK;
@@ -1500,9 +1714,7 @@ int pqd_propagate_table(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, 
                         int32_t n_out, const pqd_c128* out_ops, const pqd_traj* tr, pqd_c128* table,
                         int64_t table_len) {
     if (!tr) return fail(PQD_ERR_ARG, "NULL argument");
-    int64_t out_len = 0;
-    for (int t = 0; t < tr->n_traj; ++t)
-        out_len = std::max<int64_t>(out_len, tr->out_offset[t] + (int64_t)(tr->out_end[t] - tr->out_begin[t] + 1) * n_out);
+    const int64_t out_len = traj_out_len(tr, n_out);
     pqd_plan* P = nullptr;
     int rc = pqd_plan_create_multi(ctx, n_sys, systems, traj_sys, grid, pt, sched, rho0, n_out, out_ops, tr,
                                    std::max<int64_t>(1, out_len), &P);

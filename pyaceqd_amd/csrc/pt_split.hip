@@ -655,14 +655,8 @@ int split_occ_n(int CHI) {
 
 }  // namespace
 
-// workgroups per group: the N2 row workgroups, plus the output workgroup in the counter form unless PQD_SPLIT_OW=0
-// (the same environment the plan's SweepParams.split_gran / split_ow are read from)
-bool split_ow_env() {
-    const char* g = getenv("PQD_SPLIT_GRAN");
-    const char* o = getenv("PQD_SPLIT_OW");
-    return !(g && atoi(g) == 1) && !(o && atoi(o) == 0);
-}
-int split_group_size(int N2) { return N2 + (split_ow_env() ? 1 : 0); }
+// workgroups per group: the N2 row workgroups, plus the output workgroup (ow: the plan's SweepParams.split_ow)
+int split_group_size(int N2, bool ow) { return N2 + (ow ? 1 : 0); }
 
 // workgroups of the split kernel the runtime can keep resident per CU (0: the kernel cannot run)
 int split_blocks_per_cu(int N2, int CHI) {
@@ -676,10 +670,10 @@ int split_blocks_per_cu(int N2, int CHI) {
     }
 }
 
-bool split_supported(int N2, int CHI, int n_traj, int n_cu) {
+bool split_supported(int N2, int CHI, int n_traj, int n_cu, bool ow) {
     return (CHI == 16 || CHI == 32 || CHI == 64) &&
            (N2 == 4 || N2 == 9 || N2 == 16 || N2 == 25 || N2 == 36) && n_traj >= 1 &&
-           (long long)n_traj * split_group_size(N2) <= n_cu;
+           (long long)n_traj * split_group_size(N2, ow) <= n_cu;
 }
 
 // X: n_traj * 4 * N2 * CHI double2 exchange buffer (granules, tags zeroed here); cnt: n_traj * 64 arrival words and err,

@@ -390,6 +390,13 @@ class Plan:
         _lib.check(_lib.lib().pqd_plan_sweep_lean(self.handle, C.byref(on)))
         return bool(on.value)
 
+    def describe(self):
+        """every decision plan creation took (pqd_plan_describe) as a dict of strings: path, workgroup shape, split /
+        quad / trunk layout, windows, the A/B switches, and hashes of the block, row-unit and group tables"""
+        buf = C.create_string_buffer(2048)
+        _lib.check(_lib.lib().pqd_plan_describe(self.handle, buf, len(buf)))
+        return dict(kv.split("=", 1) for kv in buf.value.decode().split())
+
     def traj_steps(self):
         """trajectory-steps one execute propagates (shared trunks counted once per workgroup)"""
         p, b, f, n = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()

@@ -42,3 +42,14 @@ def test_no_device_errors_cleanly():
         _lib.Context(0)
     assert _lib.lib().pqd_version() >= 1
     assert isinstance(_lib.lib().pqd_last_error(), bytes)
+
+
+def test_plan_describe_refuses_null_arguments():
+    """pqd_plan_describe checks its arguments before it reads the plan (no GPU needed): NULL plan, NULL buffer and a
+    non-positive length are PQD_ERR_ARG with a message; tests/test_gpu_plan_choice.py covers a real plan's short buffer"""
+    L = _lib.lib()
+    buf = C.create_string_buffer(16)
+    assert L.pqd_plan_describe(None, buf, len(buf)) == 1
+    assert L.pqd_last_error()
+    assert L.pqd_plan_describe(None, None, 0) == 1
+
