@@ -389,6 +389,164 @@ __device__ __forceinline__ void pt_rows3(const double2* __restrict__ Qg, double2
     pt_rows3_n<N2, CHI, BT, RS, TS, PF, BT / 4>(Qg, st, e, lane);
 }
 
+// The PT phase of the lean instance (chi = 64, BT = 8: two row blocks, four column groups, 16 k-steps): the wave's one
+// or two units in one routine, the k-steps of a unit fully unrolled. Same MFMAs with the same operands in the same order
+// per accumulator, the same operand sums and the same combine as pt_row_mfma3, so the results are bit-identical to it.
+// What differs is where the non-MFMA instructions go (they cost matrix-pipe time on gfx950):
+//   * slice loads: wave-uniform 64-bit base (slice of the step's set, k-step folded in) + one 32-bit lane offset `qoff`
+//     computed before the step loop + the column group as the instruction's immediate: no vector address arithmetic;
+//   * state rows: one LDS address per row block and row of the unit, k-steps through the DS immediate (64 B each);
+//   * the accumulators are born in k-step 0 (zero C operand), no zeroing moves and no copies at the end of the loop;
+//   * k-step ks issues the slice loads of ks + PF and the LDS reads of ks + 1 before its own MFMAs (sched_barrier keeps
+//     the k-steps apart; the waits the compiler derives in straight-line code are counted and reach 0 only where
+//     nothing else is in flight: a step's first and a wave's last k-step);
+//   * a wave with two units loads the second unit's first PF k-steps in the first unit's last PF k-steps, so the slice
+//     pipeline runs through the first unit's combine and LDS writes; a wave with one unit loads nothing more.
+// Bounds: every slice load is base-of-slice + qoff + constant with qoff <= 3 * CHI * 16 + 15 * 16 and the constant
+// 4 ks CHI 16 + 256 g for ks < KSN, g < NG (static_assert below: the largest address is the slice's last element), and
+// the prefetch across units reads k-steps 0 .. PF - 1 of the second unit's own slice, only where that unit exists.
+// Nothing is loaded beyond the slice a unit contracts, whichever slice of the PT's buffer that is.
+template <int CHI, int RS, int TS, int PF>
+struct LeanPt {
+    static constexpr int RB = 2, NG = CHI / 16, KSN = CHI / 4;
+    static constexpr unsigned KSB = 4 * CHI * sizeof(double2);   // bytes per k-step of a slice
+    static_assert(PF >= 1 && PF < KSN, "k-steps in flight");
+    static_assert((KSN - 1) * KSB + (NG - 1) * 256 + 3 * CHI * sizeof(double2) + 15 * sizeof(double2) ==
+                      (size_t)CHI * CHI * sizeof(double2) - sizeof(double2), "the last load ends with the slice");
+
+    typedef __attribute__((address_space(1))) char GlobalBytes;
+    typedef double dbl2 __attribute__((ext_vector_type(2)));   // a complex double without the address-space-bound class
+    typedef __attribute__((address_space(3))) dbl2 LdsC2;
+    // k-step ks of the slice at the wave-uniform address Qu. The base of the k-step is pinned to scalar registers, so
+    // the loads take the form (scalar base) + (32-bit lane offset) + immediate
+    static __device__ __forceinline__ void ldq(dbl2 (&q)[NG], const double2* Qu, unsigned qoff, int ks) {
+        unsigned long long b = (unsigned long long)Qu + (size_t)ks * KSB;
+        asm("" : "+s"(b));
+        asm("" : "+v"(qoff));   // keeps the offset's zero extension beside the loads (selects the scalar-base form)
+        const GlobalBytes* bp = (const GlobalBytes*)b;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) q[g] = *(const __attribute__((address_space(1))) dbl2*)(bp + (size_t)qoff + 256 * g);
+    }
+    static __device__ __forceinline__ void ldq_first(dbl2 (&qn)[PF][NG], const double2* Qu, unsigned qoff) {
+#pragma unroll
+        for (int f = 0; f < PF; ++f) ldq(qn[f], Qu, qoff, f);
+    }
+
+    // the pinned LDS address of row a of row block rb behind the lane's part p: one register per row and row block
+    // (4 TS double2 apart: beyond the DS immediate), so that the k-steps and column groups stay in the immediates
+    template <typename P>
+    static __device__ __forceinline__ P* lds_row(P* p, int a, int rb) {
+        unsigned v = (unsigned)(size_t)(p + a * RS + 4 * rb * TS);
+        asm("" : "+v"(v));
+        return (P*)v;
+    }
+
+    // one unit of R rows: qn holds k-steps 0 .. PF - 1 of its slice Qu on entry and, with MORE, those of the wave's
+    // next unit (slice Qnext) on return: the last PF k-steps load them in place of their own slice's.
+    // xr, wr: the rows' read and write addresses; avn: k-step 0 of the state rows (issued by the caller)
+    template <int R, bool MORE>
+    static __device__ __forceinline__ void unit(dbl2 (&qn)[PF][NG], const double2* Qu, const double2* Qnext,
+                                                unsigned qoff, const LdsC2* (&xr)[R][RB], LdsC2* (&wr)[R][RB],
+                                                dbl2 (&avn)[R][RB]) {
+        double p1[R][RB][NG], p2[R][RB][NG], p3[R][RB][NG];
+#pragma unroll
+        for (int ks = 0; ks < KSN; ++ks) {
+            __builtin_amdgcn_sched_barrier(0);
+            dbl2 qv[NG], av[R][RB];
+#pragma unroll
+            for (int g = 0; g < NG; ++g) qv[g] = qn[0][g];
+#pragma unroll
+            for (int f = 0; f + 1 < PF; ++f)
+#pragma unroll
+                for (int g = 0; g < NG; ++g) qn[f][g] = qn[f + 1][g];
+            if (ks + PF < KSN) ldq(qn[PF - 1], Qu, qoff, ks + PF);
+            else if (MORE) ldq(qn[PF - 1], Qnext, qoff, ks + PF - KSN);
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int rb = 0; rb < RB; ++rb) {
+                    av[r][rb] = avn[r][rb];
+                    if (ks + 1 < KSN) avn[r][rb] = xr[r][rb][4 * (ks + 1)];
+                }
+            double qs[NG];
+#pragma unroll
+            for (int g = 0; g < NG; ++g) qs[g] = qv[g].x + qv[g].y;
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int rb = 0; rb < RB; ++rb) {
+                    const double as = av[r][rb].x + av[r][rb].y;
+#pragma unroll
+                    for (int g = 0; g < NG; ++g) {
+                        p1[r][rb][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(av[r][rb].x, qv[g].x, ks ? p1[r][rb][g] : 0.0, 0, 0, 0);
+                        p2[r][rb][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(av[r][rb].y, qv[g].y, ks ? p2[r][rb][g] : 0.0, 0, 0, 0);
+                        p3[r][rb][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(as, qs[g], ks ? p3[r][rb][g] : 0.0, 0, 0, 0);
+                    }
+                }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+                for (int g = 0; g < NG; ++g)
+                    wr[r][rb][16 * g] = dbl2{p1[r][rb][g] - p2[r][rb][g], p3[r][rb][g] - p1[r][rb][g] - p2[r][rb][g]};
+    }
+    // unit e = (slice, row 0, row 1 or -1, -) of one or two rows; en: the wave's next unit (MORE). The first row's
+    // addresses and its k-step 0 are common to both sizes and issued ahead of the branch (and of the first wait for
+    // the slice, which the compiler places there)
+    template <bool MORE>
+    static __device__ __forceinline__ void unit_r(dbl2 (&qn)[PF][NG], const double2* Qs, int4 e, int4 en, unsigned qoff,
+                                                  const double2* xl, double2* wl) {
+        const double2* Qu = Qs + (size_t)e.x * CHI * CHI;
+        const double2* Qnext = Qs + (size_t)(MORE ? en.x : e.x) * CHI * CHI;
+        const LdsC2* x0[RB];
+        LdsC2* w0[RB];
+        dbl2 a0[RB];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) {
+            x0[rb] = lds_row((const LdsC2*)xl, e.y, rb);
+            w0[rb] = lds_row((LdsC2*)wl, e.y, rb);
+            a0[rb] = x0[rb][0];
+        }
+        if (e.z >= 0) {
+            const LdsC2* xr[2][RB];
+            LdsC2* wr[2][RB];
+            dbl2 avn[2][RB];
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) {
+                xr[0][rb] = x0[rb]; wr[0][rb] = w0[rb]; avn[0][rb] = a0[rb];
+                xr[1][rb] = lds_row((const LdsC2*)xl, e.z, rb);
+                wr[1][rb] = lds_row((LdsC2*)wl, e.z, rb);
+                avn[1][rb] = xr[1][rb][0];
+            }
+            unit<2, MORE>(qn, Qu, Qnext, qoff, xr, wr, avn);
+        } else {
+            const LdsC2* xr[1][RB];
+            LdsC2* wr[1][RB];
+            dbl2 avn[1][RB];
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) { xr[0][rb] = x0[rb]; wr[0][rb] = w0[rb]; avn[0][rb] = a0[rb]; }
+            unit<1, MORE>(qn, Qu, Qnext, qoff, xr, wr, avn);
+        }
+    }
+
+    // the wave's units u0 and u1 (slice, row 0, row 1 or -1, -; slice < 0: none) on the step's slice set Qs
+    static __device__ __forceinline__ void run(const double2* Qs, int4 u0, int4 u1, unsigned qoff, const double2* xl,
+                                               double2* wl) {
+        if (u0.x < 0) return;
+        dbl2 qn[PF][NG];
+        ldq_first(qn, Qs + (size_t)u0.x * CHI * CHI, qoff);
+        int4 e = u0;
+        if (u1.x >= 0) {
+            unit_r<true>(qn, Qs, u0, u1, qoff, xl, wl);
+            e = u1;
+        }
+        unit_r<false>(qn, Qs, e, e, qoff, xl, wl);
+    }
+};
+
 // PT contraction of row alpha for BT = 8 on v_mfma_f64_16x16x4_f64 ("split complex"): the 16 MFMA rows are
 // [Re X; Im X] of the 8 trajectories, so two real GEMMs P1 = [Xr; Xi] Qr and P2 = [Xr; Xi] Qi hold all four
 // partial products: Cr = P1[top] - P2[bottom], Ci = P2[top] + P1[bottom]. C fragment rows (l>>4) + 4 r put
@@ -443,6 +601,10 @@ __device__ __forceinline__ void pt_row_mfma16(const double2* __restrict__ Qg, do
 // exactly that configuration (pqd_host.cpp sweep_lean_ok). With that room the wave's unit list and the slice schedule
 // stay in scalar registers (200.3 -> 196.1 ms per bench launch; the instance alone gains nothing, and
 // a register for the next event step or the first slice k-step loaded before the PT barrier measured slower).
+// Its PT phase is LeanPt above (184.2 against 193.8 ms; the fused column operator loaded a phase ahead and a static
+// s_setprio for waves 4-7 both measured slower on top of it and are not here).
+// slice k-steps in flight in the lean instance's PT phase (2 measured the same within the spread and takes all 256 VGPRs)
+constexpr int LEAN_PF = 1;
 template <int N2, int CHI, int BT, bool TRUNK, bool LEAN = false>
 __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_kernel(SweepParams p, const double2* __restrict__ Mg,
                                                            const double2* __restrict__ Qg0, double2* __restrict__ outg,
@@ -557,6 +719,10 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
         sc_prev = ldc(p.sched + (n0 > 0 ? n0 - 1 : 0));
         sc_cur = ldc(p.sched + (n0 < p.n_steps ? n0 : p.n_steps - 1));
     }
+    // lean: the lane's part of the PT phase's addresses (slice offset in bytes, state-row read and write pointers)
+    const unsigned lean_qoff = (unsigned)((pq * CHI + pj) * sizeof(double2));
+    const double2* lean_xl = st + pq + (lane & 3) * TS;
+    double2* lean_wl = st + pj + pq * TS;
     for (int n = n0;; ++n) {
         // ------------------------------------------------------------ shared-trunk activations at step n
         if (n == next_act) {
@@ -686,14 +852,9 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
 
         // ------------------------------------------------------------ PT contraction
         if constexpr (LEAN) {
-            // 3M rows of this wave's one or two units, one k-step of the slice in flight (the default below)
+            // 3M rows of this wave's one or two units (LeanPt above)
             const double2* Qs = Qg0 + (size_t)sc_cur * p.D * CHI * CHI;
-#pragma nounroll
-            for (int u = 0; u < 2; ++u) {
-                const int4 e = u ? u1 : u0;
-                if (e.x < 0) break;
-                pt_rows3<N2, CHI, BT, RS, TS, 1>(Qs + (size_t)e.x * CHI * CHI, st, e, lane);
-            }
+            LeanPt<CHI, RS, TS, LEAN_PF>::run(Qs, u0, u1, lean_qoff, lean_xl, lean_wl);
         } else if (!(ablate & 1)) {
             const double2* Qs = Qg0 + (size_t)p.sched[n] * p.D * CHI * CHI;
             // pt_mode 0: VALU rows, 1: matrix-core rows (4x4x4_4b), 4: matrix-core rows with 3 real products per
