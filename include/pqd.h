@@ -15,6 +15,10 @@
  *                                   stated layout assumption (ACE_PTB_V0)
  *   pqd_free_propagators            exposes the free propagator ACEutils.FreePropagator.update(t,dt).M
  *                                   (general_system.py:324-327, `get_M_t`).
+ *   pqd_dressed_states              replaces the second binary `timedep_eigenstates` and its `.ds` file
+ *                                   (general_system.py:297-304) and the per-time eigenvector / occupation loops of
+ *                                   general_dressed_states.py:62-70, 161-165: H(t) of every (system, output time)
+ *                                   diagonalised in one launch.
  *   pqd_propagate_tau               f2py propagate_tau_module.propagate_tau   (two_time/propagate_tau.f90:3)
  *   pqd_calc_onetime_parallel       ... .calc_onetime_parallel                 (propagate_tau.f90:110)
  *   pqd_calc_onetime_parallel_block ... .calc_onetime_parallel_block           (propagate_tau.f90:189)
@@ -132,6 +136,22 @@ int pqd_ace_pt_read(const char* name, int32_t dim, const pqd_ace_pt_dims* shape,
 
 /* M_out: 2*n_steps matrices (N^2 x N^2, row-major): [2n] first half step, [2n+1] second. */
 int pqd_free_propagators(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* grid, pqd_c128* M_out);
+
+/* Dressed states: the instantaneous eigenstates of H(t_n) = H0 + sum_p (f_p(t_n) X_p + conj(f_p(t_n)) X_p^dagger) of
+ * every system at every output time t_n = ta + n dt, n = 0 .. n_steps (f_p sampled as the free propagators sample it).
+ * Replaces the `timedep_eigenstates` run (general_system.py:297-304) and the eigenvector loops of
+ * general_dressed_states.py:62-70, 161-165. Systems of equal dim in [2, 6]; lind_* and grid->n_sub are ignored.
+ * Per problem (s, n): eigenvalues ascending (ties by the solver's column index); eigenvectors of unit 2-norm,
+ * the first component of magnitude > 1e-12 real and positive; occ[j] = Re sum_{i,k} v_j[i] conj(v_j[k]) rho[i][k]
+ * (the reference's formula on the array compose_dm returns). Every output is optional (at least one is needed, occ
+ * needs rho). PQD_ERR_NUMERIC (outputs still copied) when an H entry is not finite or a problem did not converge. */
+int pqd_dressed_states(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const pqd_grid* grid,
+                       const pqd_c128* rho,   /* n_sys*(n_steps+1)*N*N or NULL */
+                       double* evals,         /* n_sys*(n_steps+1)*N        or NULL */
+                       pqd_c128* evecs,       /* n_sys*(n_steps+1)*N*N, [s][n][j][i] = component i of eigenvector j, or NULL */
+                       double* occ);          /* n_sys*(n_steps+1)*N, needs rho; or NULL */
+/* duration (ms, HIP events on the context stream) of the kernel of the context's last pqd_dressed_states call */
+int pqd_dressed_timing(pqd_ctx* ctx, double* ms_kernel);
 
 /* one-shot: upload, propagate, download. pt may be NULL (no phonons); sched[n_steps] selects the
  * PT slice per step (NULL: min(n, n_slices-1)). rho0: N*N. out_ops: n_out*N*N. */

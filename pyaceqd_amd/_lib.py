@@ -76,6 +76,9 @@ _SIGS = {
     "pqd_ace_pt_read": ([C.c_char_p, C.c_int32, C.POINTER(pqd_ace_pt_dims), P_C128, P_C128, P_C128, P_C128, P_I32],
                         C.c_int),
     "pqd_free_propagators": ([C.c_void_p, C.POINTER(pqd_system), C.POINTER(pqd_grid), P_C128], C.c_int),
+    "pqd_dressed_states": ([C.c_void_p, C.c_int32, C.POINTER(pqd_system), C.POINTER(pqd_grid), P_C128, P_F64, P_C128,
+                            P_F64], C.c_int),
+    "pqd_dressed_timing": ([C.c_void_p, P_F64], C.c_int),
     "pqd_propagate": ([C.c_void_p, C.POINTER(pqd_system), C.POINTER(pqd_grid), C.c_void_p, P_I32, P_C128,
                        C.c_int32, P_C128, C.POINTER(pqd_traj), P_C128, C.c_int64], C.c_int),
     "pqd_propagate_multi": ([C.c_void_p, C.c_int32, C.POINTER(pqd_system), P_I32, C.POINTER(pqd_grid), C.c_void_p,

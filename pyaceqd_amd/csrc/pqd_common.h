@@ -271,7 +271,28 @@ struct FourTimeParams {
     double2* result;         // (n_t, n_t) column-major
 };
 
+// dressed states (dressed.hip): H(t_n) of every system on the output grid, diagonalised
+struct DressedSys {            // one system: the Hamiltonian parts themselves (FreePropSys holds superoperators)
+    const double2* H0;       // N*N, row-major
+    const double2* X;        // n_chan*N*N channel operators X_p
+    const double2* samples;  // n_chan*n_samples
+    int n_chan, n_samples;
+    double s_t0, s_dt;
+};
+
+struct DressedParams {
+    const DressedSys* systems;  // device table, n_sys entries
+    int n_sys, n_steps;         // problems: (system s, output time n), n = 0 .. n_steps, index s * (n_steps + 1) + n
+    double ta, dt;
+    const double2* rho;      // [problem][N][N] or NULL (needed by occ)
+    double* evals;           // [problem][N] ascending, or NULL
+    double2* evecs;          // [problem][j][i] = component i of eigenvector j, or NULL
+    double* occ;             // [problem][N], or NULL
+    unsigned* flags;         // bit 0: a non-finite H entry, bit 1: a problem not converged after the sweep limit
+};
+
 // launchers (defined in the .hip translation units)
+hipError_t launch_dressed(int N, const DressedParams& p, hipStream_t s);
 struct FuseParams {          // F(m) = M_a(m) M_b(m-1) (1 <= m < n_steps), W(m) = ovec . M_b(m-1) (1 <= m <= n_steps)
     const double2* M;
     double2* F;

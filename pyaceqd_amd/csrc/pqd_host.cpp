@@ -183,6 +183,7 @@ struct pqd_ctx {
     hipStream_t stream = nullptr;
     // map-chain sweeps: one device arena reused across calls (grown on demand), so a call allocates nothing
     DevBuf<char> mc_arena;
+    double dressed_ms = -1.0;  // kernel duration of the last pqd_dressed_states call (pqd_dressed_timing)
 };
 
 namespace {
@@ -530,6 +531,109 @@ int pqd_free_propagators(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* gr
     HIPCHK(launch_free_prop(N2, fp, s));
     if (nM) HIPCHK(hipMemcpyAsync(M_out, M.p, nM * sizeof(double2), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return PQD_OK;
+}
+
+// Dressed states: H0, the channel operators and the samples of every system go up as they are (no generators: the
+// kernel diagonalises H itself), one kernel solves every (system, output time), the requested outputs come back.
+int pqd_dressed_states(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const pqd_grid* grid,
+                       const pqd_c128* rho, double* evals, pqd_c128* evecs, double* occ) {
+    if (!evals && !evecs && !occ) return fail(PQD_ERR_ARG, "no output requested (evals, evecs and occ are all NULL)");
+    if (occ && !rho) return fail(PQD_ERR_ARG, "occ needs rho");
+    if (n_sys < 1 || !systems) return fail(PQD_ERR_ARG, "need at least one system");
+    for (int k = 0; k < n_sys; ++k) {  // check_system without the Lindblad terms and hbar, which H(t) does not hold
+        const pqd_system& y = systems[k];
+        if (y.dim < 2 || y.dim > 6) return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [2, 6]", y.dim);
+        if (!y.H0) return fail(PQD_ERR_ARG, "H0 is NULL");
+        if (y.n_chan < 0 || y.n_chan > 4) return fail(PQD_ERR_UNSUPPORTED, "n_chan %d not in [0, 4]", y.n_chan);
+        if (y.n_chan > 0 && (!y.chan_ops || !y.chan_samples || y.n_samples < 1 || !(y.sample_dt > 0)))
+            return fail(PQD_ERR_ARG, "bad pulse-channel arguments");
+        if (systems[k].dim != systems[0].dim)
+            return fail(PQD_ERR_UNSUPPORTED, "systems of unequal dim (%d and %d)", systems[0].dim, systems[k].dim);
+    }
+    if (!grid) return fail(PQD_ERR_ARG, "grid is NULL");
+    if (grid->n_steps < 0) return fail(PQD_ERR_ARG, "n_steps < 0");
+    if (!(grid->dt > 0)) return fail(PQD_ERR_ARG, "dt must be > 0");
+    if (!ctx) return fail(PQD_ERR_ARG, "ctx is NULL");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int N = systems[0].dim;
+    const size_t nn = (size_t)N * N, n_prob = (size_t)n_sys * ((size_t)grid->n_steps + 1);
+
+    std::vector<cd> h0(n_sys * nn), xs, sm;
+    std::vector<size_t> oX(n_sys), oM(n_sys);
+    for (int k = 0; k < n_sys; ++k) {
+        const pqd_system& y = systems[k];
+        std::copy(C(y.H0), C(y.H0) + nn, h0.begin() + k * nn);
+        oX[k] = xs.size();
+        oM[k] = sm.size();
+        if (y.n_chan > 0) {
+            xs.insert(xs.end(), C(y.chan_ops), C(y.chan_ops) + (size_t)y.n_chan * nn);
+            sm.insert(sm.end(), C(y.chan_samples), C(y.chan_samples) + (size_t)y.n_chan * y.n_samples);
+        }
+    }
+    if (xs.empty()) xs.assign(1, 0.0);
+    if (sm.empty()) sm.assign(1, 0.0);
+    DevBuf<double2> dH0, dX, dS, dRho, dVec;
+    DevBuf<double> dVal, dOcc;
+    DevBuf<DressedSys> tab;
+    DevBuf<unsigned> flags;
+    HIPCHK(dH0.upload(reinterpret_cast<double2*>(h0.data()), h0.size(), s));
+    HIPCHK(dX.upload(reinterpret_cast<double2*>(xs.data()), xs.size(), s));
+    HIPCHK(dS.upload(reinterpret_cast<double2*>(sm.data()), sm.size(), s));
+    std::vector<DressedSys> t(n_sys);
+    for (int k = 0; k < n_sys; ++k) {
+        const pqd_system& y = systems[k];
+        t[k].H0 = dH0.p + k * nn;
+        t[k].X = dX.p + oX[k];
+        t[k].samples = dS.p + oM[k];
+        t[k].n_chan = y.n_chan;
+        t[k].n_samples = std::max(1, y.n_samples);
+        t[k].s_t0 = y.sample_t0;
+        t[k].s_dt = y.n_chan > 0 ? y.sample_dt : 1.0;
+    }
+    HIPCHK(tab.upload(t.data(), t.size(), s));
+    if (occ) HIPCHK(dRho.upload(reinterpret_cast<const double2*>(rho), n_prob * nn, s));
+    if (evals) HIPCHK(dVal.alloc(n_prob * N));
+    if (evecs) HIPCHK(dVec.alloc(n_prob * nn));
+    if (occ) HIPCHK(dOcc.alloc(n_prob * N));
+    HIPCHK(flags.alloc(1));
+    HIPCHK(hipMemsetAsync(flags.p, 0, sizeof(unsigned), s));
+
+    DressedParams dp{};
+    dp.systems = tab.p; dp.n_sys = n_sys; dp.n_steps = grid->n_steps;
+    dp.ta = grid->ta; dp.dt = grid->dt;
+    dp.rho = dRho.p; dp.evals = dVal.p; dp.evecs = dVec.p; dp.occ = dOcc.p; dp.flags = flags.p;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(hipEventCreate(&e0));
+    hipError_t he = hipEventCreate(&e1);
+    if (he == hipSuccess) he = hipEventRecord(e0, s);
+    if (he == hipSuccess) he = launch_dressed(N, dp, s);
+    if (he == hipSuccess) he = hipEventRecord(e1, s);
+    unsigned hf = 0;
+    if (he == hipSuccess && evals)
+        he = hipMemcpyAsync(evals, dVal.p, n_prob * N * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (he == hipSuccess && evecs)
+        he = hipMemcpyAsync(evecs, dVec.p, n_prob * nn * sizeof(double2), hipMemcpyDeviceToHost, s);
+    if (he == hipSuccess && occ)
+        he = hipMemcpyAsync(occ, dOcc.p, n_prob * N * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(&hf, flags.p, sizeof(unsigned), hipMemcpyDeviceToHost, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    float ms = -1.0f;
+    if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (he != hipSuccess) return fail(PQD_ERR_HIP, "pqd_dressed_states: %s", hipGetErrorString(he));
+    ctx->dressed_ms = ms;
+    if (hf & 1u) return fail(PQD_ERR_NUMERIC, "pqd_dressed_states: H(t) holds a non-finite entry");
+    if (hf & 2u) return fail(PQD_ERR_NUMERIC, "pqd_dressed_states: a problem did not converge in 30 Jacobi sweeps");
+    return PQD_OK;
+}
+
+int pqd_dressed_timing(pqd_ctx* ctx, double* ms_kernel) {
+    if (!ctx || !ms_kernel) return fail(PQD_ERR_ARG, "NULL argument");
+    if (ctx->dressed_ms < 0) return fail(PQD_ERR_ARG, "no pqd_dressed_states call on this context yet");
+    *ms_kernel = ctx->dressed_ms;
     return PQD_OK;
 }
 

@@ -340,6 +340,67 @@ def free_propagators(system: System, grid: Grid, ctx=None):
     return M[: 2 * grid.n_steps]
 
 
+DRESSED_LAUNCHES = 0  # pqd_dressed_states calls issued by this process (tests count launches with it)
+
+
+def dressed_states(system_or_systems, grid: Grid, rho=None, want_vectors=True, ctx=None):
+    """Dressed states of every system at every output time of `grid` in one launch (pqd_dressed_states): the
+    eigenpairs of H(t_n) = H0 + sum_p (f_p(t_n) X_p + h.c.), Lindblad terms and n_sub ignored.
+
+    Returns (evals, evecs, occ), each with leading axes (n_sys, n_steps + 1), or (n_steps + 1,) when a single System
+    (not a list) was passed: evals (..., N) ascending; evecs (..., N, N) with evecs[..., j, i] = component i of
+    eigenvector j (unit norm, first component above 1e-12 real and positive), None when want_vectors is False;
+    occ (..., N) = Re sum_ik v_j[i] conj(v_j[k]) rho[..., i, k] for rho of shape (n_sys, n_steps + 1, N, N) (the
+    reference's formula, general_dressed_states.py:161-165), None when rho is None."""
+    global DRESSED_LAUNCHES
+    ctx = ctx or _lib.context()
+    single = not isinstance(system_or_systems, (list, tuple))
+    systems = _systems(system_or_systems)
+    N = systems[0].dim
+    if any(s.dim != N for s in systems):
+        raise ValueError("all systems of a batch must have the same dimension")
+    n_sys, n_t = len(systems), int(grid.n_steps) + 1
+    r = None
+    if rho is not None:
+        r = _c(rho)
+        if r.size != n_sys * n_t * N * N:
+            raise ValueError(f"rho has {r.size} elements, {n_sys} systems x {n_t} times x {N} x {N} are needed")
+        r = r.reshape(n_sys, n_t, N, N)
+    evals = np.empty((n_sys, n_t, N), dtype=np.float64)
+    evecs = np.empty((n_sys, n_t, N, N), dtype=np.complex128) if want_vectors else None
+    occ = np.empty((n_sys, n_t, N), dtype=np.float64) if r is not None else None
+    with ctx.lock:
+        convs = [s.to_c() for s in systems]
+        sc = (_lib.pqd_system * n_sys)(*[c for c, _ in convs])
+        gc = grid.to_c()
+        DRESSED_LAUNCHES += 1
+        _lib.check(_lib.lib().pqd_dressed_states(ctx.handle, n_sys, sc, C.byref(gc), _lib.cptr(r), _lib.fptr(evals),
+                                                 _lib.cptr(evecs), _lib.fptr(occ)))
+    if single:
+        return evals[0], None if evecs is None else evecs[0], None if occ is None else occ[0]
+    return evals, evecs, occ
+
+
+def dressed_kernel_ms(ctx=None):
+    """kernel duration (ms, device events) of the context's last dressed_states call"""
+    ctx = ctx or _lib.context()
+    ms = C.c_double()
+    _lib.check(_lib.lib().pqd_dressed_timing(ctx.handle, C.byref(ms)))
+    return ms.value
+
+
+def dressed_table(times, evals, evecs):
+    """The table the reference reads from timedep_eigenstates' `.ds` file (general_dressed_states.py:62-70): complex
+    (1 + N + N^2, n_t), row 0 = time, rows 1..N the eigenvalues, row 1 + N + i N + j = component j of eigenvector i."""
+    evals = np.asarray(evals)
+    n_t, N = evals.shape
+    tab = np.empty((1 + N + N * N, n_t), dtype=np.complex128)
+    tab[0] = times
+    tab[1: 1 + N] = evals.T
+    tab[1 + N:] = np.asarray(evecs).reshape(n_t, N * N).T
+    return tab
+
+
 class Plan:
     """Device-resident propagation job for repeated execution (bench.py, parameter scans)."""
 

@@ -10,7 +10,7 @@ from .. import constants
 hbar = constants.hbar
 temp_dir = constants.temp_dir
 
-_FWD = ("trajectories", "n_sub", "device", "rho0", "get_M_t", "pulse_sampling", "trapz")
+_FWD = ("trajectories", "n_sub", "device", "rho0", "get_M_t", "pulse_sampling", "trapz", "dressed_rho")
 
 
 def biexciton_ops(delta_xy=0, shift_x=True, coupl_xy=0, delta_b=4, gamma_e=1/100, gamma_b=None, lindblad=False,
@@ -50,3 +50,14 @@ def biexciton(t_start, t_end, *pulses, dt=0.5, delta_xy=0, shift_x=True, coupl_x
         boson_op=boson_op, initial=initial, lindblad_ops=lindblad_ops, interaction_ops=interaction_ops,
         output_ops=output_ops, prepare_only=prepare_only, dressedstates=dressedstates, rf_op=rf_op, rf_file=rf_file,
         firstonly=firstonly, use_infinite=use_infinite, calc_dynmap=calc_dynmap, **fwd)
+
+
+def biexciton_dressed_states(t_start, t_end, *pulses, plot=True, t_lim=None, e_lim=None,
+                             colors=["#0000FF", "#00CC33", "#F9A627", "#FF0000"], filename="biexciton_dressed",
+                             firstonly=False, visible_states=None, return_eigenvectors=False, **options):
+    """Dressed states of the driven biexciton cascade (pyaceqd/four_level_system/linear.py:41-43): the reference's
+    tuple t, populations, e_values, ds_occ, s_colors, n_colors[, e_vectors, rho]."""
+    from ..general_system.general_dressed_states import dressed_states
+    return dressed_states(biexciton, 4, t_start, t_end, *pulses, filename=filename, t_lim=t_lim, e_lim=e_lim,
+                          plot=plot, firstonly=firstonly, colors=colors, visible_states=visible_states,
+                          return_eigenvectors=return_eigenvectors, **options)

@@ -31,7 +31,7 @@ from .. import constants
 from .._lib import PQDError, PQD_ERR_UNSUPPORTED
 from .. import opgrammar
 from ..engine import Grid, MTO, ProcessTensor, System, Trajectories, free_propagators, propagate, propagate_table, \
-    propagate_trapz, KIND
+    propagate_trapz, KIND, dressed_states, dressed_table
 
 temp_dir = constants.temp_dir
 
@@ -238,7 +238,7 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
                       prepare_only=False, LO_params=None, dressedstates=False, rf_op=None, rf_file=None,
                       firstonly=False, J_to_file=None, J_file=None, factor_ah=None, use_infinite=False,
                       print_H=False, calc_dynmap=False, rho0=None, get_M_t=None, trajectories=None, n_sub=1,
-                      device=None, pulse_sampling="ace_file", trapz=None):
+                      device=None, pulse_sampling="ace_file", trapz=None, dressed_rho=None):
     """Propagate one trajectory (or a batch: `trajectories`) and return ACE's output table.
 
     Returns (1 + len(output_ops), n_t) complex, row 0 = time (general_system.py:104-110, 343).
@@ -255,6 +255,13 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
     dt/(4 n_sub) instead, so every exponential midpoint is a sample of the analytic field. The two differ by
     O(dt^2 f'') (about 1e-4 relative for tau_0 = 3 ps at dt = 0.1), above the no-phonon 1e-8 tolerance, which is
     why the drop-in default is the reference's.
+
+    dressedstates=True returns, in place of the propagation table, the table the reference reads from
+    timedep_eigenstates' `.ds` file (:297-304): complex (1 + N + N^2, n_t) on the same output grid, row 0 = time,
+    rows 1..N the eigenvalues of H(t) (ascending), row 1 + N + i N + j = component j of eigenvector i
+    (general_dressed_states.py:64-70); one table per trajectory with `trajectories`, all from one launch
+    (pqd_dressed_states; semantic choices in DESIGN.md §2). dressed_rho (one (n_t, N, N) array per trajectory) makes
+    every entry a (table, occupations (n_t, N)) pair, the occupations evaluated in the same launch.
     """
     if pulse_sampling not in ("exact", "ace_file"):
         raise ValueError(f"pulse_sampling must be 'exact' or 'ace_file', not {pulse_sampling!r}")
@@ -268,8 +275,9 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
         _write_J(J_to_file, ae, factor_ah, J_file)
     if prepare_only:
         return [np.array([0, 0]) for _ in range(1 + len(output_ops))]
-    if dressedstates or print_H:
-        raise NotImplementedError("dressed-state / print_H diagnostics are out of scope (SURVEY.md §2)")
+    if print_H:
+        raise NotImplementedError("print_H is out of scope: the `.ham` file the reference's binary writes cannot be "
+                                  "inferred offline (SURVEY.md §2)")
     if LO_params is not None:
         raise NotImplementedError("add_single_mode (LO phonons) is out of scope (SURVEY.md §2)")
 
@@ -389,6 +397,34 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
             systems.append(make_system(pl, pfx, pfy, hamiltonian(sop), dissipators(lop)))
         traj_sys.append(sys_keys[key])
     system = systems[0]
+
+    if dressedstates:
+        # the table the reference reads from timedep_eigenstates' `.ds` file (:297-304): the eigenpairs of the param
+        # file's H(t) on the output grid, every distinct drive in one launch (pqd_dressed_states). No PT, no Lindblad
+        # terms, no propagation
+        from .. import _lib
+        n_ts = [(traj_steps[k] if trajectories is not None else n_steps) + 1 for k in range(len(traj_specs))]
+        if dressed_rho is None:
+            pick = traj_sys
+            ev, vec, occ = dressed_states(systems, grid, ctx=_lib.context(device))
+        else:
+            # one problem set per trajectory, with its density matrices (rows past a shorter trajectory's end stay 0)
+            if len(dressed_rho) != len(traj_specs):
+                raise ValueError("dressed_rho needs one (n_t, dim, dim) array per trajectory")
+            rho_all = np.zeros((len(traj_specs), n_steps + 1, dim, dim), dtype=complex)
+            for k, r in enumerate(dressed_rho):
+                r = np.asarray(r)
+                if r.shape != (n_ts[k], dim, dim):
+                    raise ValueError(f"dressed_rho[{k}] has shape {r.shape}, expected {(n_ts[k], dim, dim)}")
+                rho_all[k, :n_ts[k]] = r
+            pick = range(len(traj_specs))
+            ev, vec, occ = dressed_states([systems[i] for i in traj_sys], grid, rho=rho_all,
+                                          ctx=_lib.context(device))
+        tabs = []
+        for k, i in enumerate(pick):
+            tab = dressed_table(grid.times[:n_ts[k]], ev[i][:n_ts[k]], vec[i][:n_ts[k]])
+            tabs.append(tab if dressed_rho is None else (tab, occ[i][:n_ts[k]]))
+        return tabs if trajectories is not None else tabs[0]
 
     if get_M_t is not None:
         g1 = Grid(get_M_t, dt, 1, n_sub)

@@ -21,7 +21,7 @@ g_ez = -0.8   # out of plane electron g factor
 g_hx = -0.35  # in plane hole g factor
 g_hz = -2.2   # out of plane hole g factor
 
-_FWD = ("trajectories", "n_sub", "device", "rho0", "get_M_t", "calc_dynmap", "pulse_sampling", "trapz")
+_FWD = ("trajectories", "n_sub", "device", "rho0", "get_M_t", "calc_dynmap", "pulse_sampling", "trapz", "dressed_rho")
 
 
 def energies_linear(d0=0.25, d1=0.12, d2=0.05, delta_B=4, delta_E=0.0):
@@ -97,3 +97,17 @@ def sixls_linear(t_start, t_end, *pulses, dt=0.5, delta_b=4, gamma_e=1/100, gamm
             return [compose_dm(r, dim=6) for r in result]
         return compose_dm(result, dim=6)
     return result
+
+
+def sixls_linear_dressed_states(t_start, t_end, *pulses, plot=True, t_lim=None, e_lim=None,
+                                filename="sixls_linear_dressed", firstonly=False, visible_states=None,
+                                print_states=None, return_eigenvectors=False, no_pulse=False, **options):
+    """Dressed states of the six-level dot (pyaceqd/six_level_system/linear.py:74-78): the reference's tuple
+    t, populations, e_values, ds_occ, s_colors, n_colors[, e_vectors, rho]. no_pulse diagonalises H without the
+    pulses: the field-mixed basis (bx, bz) that tools.rotate_basis turns rho into."""
+    from ..general_system.general_dressed_states import dressed_states
+    colors = ["#0000cf", "#45b0ee", "#ff0022", "#9966cc", "#009e00", "#ffde39"]
+    return dressed_states(sixls_linear, 6, t_start, t_end, *pulses, filename=filename, plot=plot, t_lim=t_lim,
+                          e_lim=e_lim, firstonly=firstonly, colors=colors, visible_states=visible_states,
+                          return_eigenvectors=return_eigenvectors, print_states=print_states, no_pulse=no_pulse,
+                          **options)

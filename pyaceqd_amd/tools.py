@@ -165,6 +165,15 @@ def output_ops_dm(dim=[2, 2], readable=False):
     return matrix_element_operators(generate_basis_states(dim), dim, readable=readable)
 
 
+def rotate_basis(rho, U_rot):
+    """rho in the basis whose states are the rows of U_rot: U_rot @ rho @ U_rot^dagger (tools.py:375-398), on one
+    matrix or a stack (n_t, N, N). With a magnetic field mixing the basis states, U_rot comes from the dressed states:
+        t, _, _, _, _, _, e_vectors, rho = sixls_linear_dressed_states(0, 1, p1, lindblad=True, bx=bx,
+                                                                      return_eigenvectors=True, no_pulse=True)
+        rho_rotated = rotate_basis(rho, e_vectors[0])"""
+    return U_rot @ rho @ np.conjugate(U_rot).T
+
+
 def op_to_matrix(op):
     """Operator string -> matrix (full ACE grammar via opgrammar, not only single |n><m|_d terms)."""
     return opgrammar.to_matrix(op)

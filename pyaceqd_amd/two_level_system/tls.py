@@ -11,7 +11,7 @@ from .. import constants
 hbar = constants.hbar
 temp_dir = constants.temp_dir
 
-_FWD = ("trajectories", "n_sub", "device", "pulse_sampling", "trapz")
+_FWD = ("trajectories", "n_sub", "device", "pulse_sampling", "trapz", "dressed_rho")
 
 
 def tls(t_start, t_end, *pulses, dt=0.1, gamma_e=1/100, phonons=False, t_mem=6.4, ae=5.0, temperature=4,
@@ -40,3 +40,16 @@ def tls(t_start, t_end, *pulses, dt=0.1, gamma_e=1/100, phonons=False, t_mem=6.4
         output_ops=output_ops, prepare_only=prepare_only, LO_params=LO_params, dressedstates=dressedstates,
         rf_op=rf_op, rf_file=rf_file, firstonly=firstonly, J_to_file=J_to_file, J_file=J_file,
         factor_ah=factor_ah, use_infinite=use_infinite, calc_dynmap=calc_dynmap, rho0=rho0, get_M_t=get_M_t, **fwd)
+
+
+def tls_dressed_states(t_start, t_end, *pulses, plot=True, t_lim=None, e_lim=None, filename="tls_dressed",
+                       firstonly=False, colors=["#0000FF", "#FF0000"], visible_states=None,
+                       return_eigenvectors=False, **options):
+    """Dressed states of the driven two-level system (pyaceqd/two_level_system/tls.py:79-87): the reference's tuple
+    t, populations, e_values, ds_occ, s_colors, n_colors[, e_vectors, rho]. RGBA colours hide states as
+    visible_states does, e.g. ["#0000FF00", "#FF0000FF"]. trajectories=[{"pulses": ...}, ...] gives one tuple per
+    drive (general_dressed_states.dressed_states)."""
+    from ..general_system.general_dressed_states import dressed_states
+    return dressed_states(tls, 2, t_start, t_end, *pulses, filename=filename, plot=plot, t_lim=t_lim, e_lim=e_lim,
+                          firstonly=firstonly, colors=colors, visible_states=visible_states,
+                          return_eigenvectors=return_eigenvectors, **options)
