@@ -154,7 +154,11 @@ int pqd_dressed_states(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, c
 int pqd_dressed_timing(pqd_ctx* ctx, double* ms_kernel);
 
 /* one-shot: upload, propagate, download. pt may be NULL (no phonons); sched[n_steps] selects the
- * PT slice per step (NULL: min(n, n_slices-1)). rho0: N*N. out_ops: n_out*N*N. */
+ * PT slice per step (NULL: min(n, n_slices-1)). rho0: N*N. out_ops: n_out*N*N.
+ * Limits (PQD_ERR_UNSUPPORTED beyond them), for this call and every propagate / plan call below: with a PT dim in
+ * [2, 6]; without one dim in [2, 24], where dim > 6 takes at most 8 jump operators and a Liouvillian whose norm bound
+ * times a sub-step stays below 4096 (PQD_PATH_HILBERT); n_chan <= 4. pqd_pt_create, pqd_free_propagators,
+ * pqd_dressed_states and the map-chain calls keep dim <= 6. */
 int pqd_propagate(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* grid, const pqd_pt* pt,
                   const int32_t* sched, const pqd_c128* rho0, int32_t n_out, const pqd_c128* out_ops,
                   const pqd_traj* traj, pqd_c128* out, int64_t out_len);
@@ -221,6 +225,9 @@ int pqd_plan_trapz(pqd_plan* plan, int32_t n_pairs, const int32_t* k_head, const
 #define PQD_PATH_SPLIT 2    /* one trajectory over N^2 workgroups (latency path) */
 #define PQD_PATH_QUAD 3     /* two-level system: four trajectories per wave set, state in registers (pt_quad.hip) */
 #define PQD_PATH_MSPLIT 4   /* several trajectories per split group: row g of TB trajectories per workgroup (pt_msplit.hip) */
+#define PQD_PATH_HILBERT 5  /* no PT, dim 7..24 (dim <= 6 under PQD_HILBERT=1): one workgroup per trajectory, rho as an
+                               N x N matrix, exp(L w) applied matrix-free (lind_hilbert.hip). bt is 1, there are no free
+                               propagators (rebuild_free is ignored, ms_free is 0, no windows, no lean instance) */
 /* the path the plan runs now, its trajectories per workgroup, how many split launches fell back, and the
  * trajectory-steps one execute propagates (trajectories of one system that share a lock-step workgroup propagate
  * their common MTO-free trunk once: PQD_BRANCH) */

@@ -18,6 +18,9 @@ class PQDError(RuntimeError):
 
 
 PQD_ERR_UNSUPPORTED = 3
+PQD_PATH_NOPT = 0
+PQD_PATH_HILBERT = 5  # no PT, dim 7..24 (dim <= 6 under PQD_HILBERT=1): the Hilbert-space kernel (include/pqd.h)
+HILBERT_MAX_DIM = 24  # largest dim of a plan without PT; everything that builds N^2 x N^2 superoperators stops at 6
 
 
 class NumericError(PQDError):

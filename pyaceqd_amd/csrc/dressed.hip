@@ -26,20 +26,6 @@ constexpr int DS_PPB = DS_THREADS / DS_LPM;   // problems per workgroup
 constexpr int DS_MAX_SWEEPS = 30;
 constexpr long long DS_MAX_BLOCKS = 1LL << 22;  // the dispatch grid counts work-items in 32 bits: larger batches loop
 
-// the free propagators' sampling (free_prop.hip sample_ch, restated on DressedSys): linear interpolation, clamped at
-// both ends
-__device__ __forceinline__ double2 ds_sample_ch(const DressedSys& p, int c, double t) {
-    const double2* f = p.samples + (size_t)c * p.n_samples;
-    const int ns = p.n_samples;
-    const double u = (t - p.s_t0) / p.s_dt;
-    if (!(u > 0.0)) return f[0];
-    if (u >= (double)(ns - 1)) return f[ns - 1];
-    const int k = (int)floor(u);
-    const double w = u - (double)k;
-    const double2 a = f[k], b = f[k + 1];
-    return make_double2(a.x + w * (b.x - a.x), a.y + w * (b.y - a.y));
-}
-
 __device__ __forceinline__ double2 c_shfl(double2 v, int src) {
     return make_double2(__shfl(v.x, src), __shfl(v.y, src));
 }
@@ -147,7 +133,7 @@ __global__ __launch_bounds__(DS_THREADS) void dressed_kernel(DressedParams p) {
                 A[r] = make_double2(a.x + b.x, a.y - b.y);
             }
             for (int ch = 0; ch < sy.n_chan; ++ch) {
-                const double2 f = ds_sample_ch(sy, ch, t);
+                const double2 f = sample_ch(sy, ch, t);  // pqd_common.h: the free propagators' sampling
                 const double2* X = sy.X + (size_t)ch * N * N;
 #pragma unroll
                 for (int r = 0; r < N; ++r) {

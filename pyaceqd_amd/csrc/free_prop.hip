@@ -20,18 +20,6 @@ constexpr long long FP_MAX_BLOCKS = 1LL << 22;
 
 namespace {
 
-__device__ __forceinline__ double2 sample_ch(const FreePropSys& p, int c, double t) {
-    const double2* f = p.samples + (size_t)c * p.n_samples;
-    const int ns = p.n_samples;
-    const double u = (t - p.s_t0) / p.s_dt;
-    if (!(u > 0.0)) return f[0];
-    if (u >= (double)(ns - 1)) return f[ns - 1];
-    const int k = (int)floor(u);
-    const double w = u - (double)k;
-    const double2 a = f[k], b = f[k + 1];
-    return make_double2(a.x + w * (b.x - a.x), a.y + w * (b.y - a.y));
-}
-
 // a half step is idle when every channel sample at every sub-step midpoint is exactly zero: then
 // L(t) = L0 + 0 S + 0 T is bitwise L0, and its propagator is the system's Midle (built by the idle pass with the
 // same code and zero samples), so it is copied instead of recomputed. Pulses are localised: the TLS scans

@@ -112,6 +112,21 @@ struct FreePropSys {           // one system of a (possibly multi-system) plan
     double s_t0, s_dt;
 };
 
+// channel c of a system at time t: linear interpolation between the samples, clamped at both ends (one definition
+// for every kernel that samples a pulse: SYS is FreePropSys or HilbertSys)
+template <class SYS>
+__device__ __forceinline__ double2 sample_ch(const SYS& p, int c, double t) {
+    const double2* f = p.samples + (size_t)c * p.n_samples;
+    const int ns = p.n_samples;
+    const double u = (t - p.s_t0) / p.s_dt;
+    if (!(u > 0.0)) return f[0];
+    if (u >= (double)(ns - 1)) return f[ns - 1];
+    const int k = (int)floor(u);
+    const double w = u - (double)k;
+    const double2 a = f[k], b = f[k + 1];
+    return make_double2(a.x + w * (b.x - a.x), a.y + w * (b.y - a.y));
+}
+
 struct FreePropParams {
     const FreePropSys* systems;  // device table, n_sys entries
     int n_sys;
@@ -290,6 +305,50 @@ struct DressedParams {
     double* occ;             // [problem][N], or NULL
     unsigned* flags;         // bit 0: a non-finite H entry, bit 1: a problem not converged after the sweep limit
 };
+
+// Hilbert-space Lindblad propagation without a PT (lind_hilbert.hip): N x N operators only, no superoperator
+constexpr int HB_NMAX = 24;        // largest Hilbert dimension
+constexpr int HB_LMAX = 8;         // most jump operators per system
+constexpr int HB_CSR_LDS = 32768;  // bytes of LDS for the jump operators' nonzero lists (larger lists stay in global memory)
+constexpr int HB_SMAX = 4096;      // most Taylor factors per sub-step (pqd_host.cpp refuses a plan whose bound needs more)
+constexpr int HB_DEGMAX = 18;      // largest Taylor degree (as free_prop.hip)
+struct HilbertSys {            // one system: everything row-major N x N, uploaded once per system
+    const double2* K0;       // -(i/hbar) H0 - 1/2 sum_k gamma_k A_k^dag A_k
+    const double2* Xs;       // n_chan: -(i/hbar) X_p
+    const double2* Xt;       // n_chan: -(i/hbar) X_p^dag
+    const double2* samples;  // n_chan*n_samples
+    int n_chan, n_samples;
+    double s_t0, s_dt;
+    int n_lind;
+    // nonzeros of the jump operators by rows: those of row i of A_k are z in [rowptr[k (N + 1) + i], rowptr[k (N + 1) + i + 1])
+    const int* rowptr;       // n_lind*(N+1), offsets into col / val
+    const int* col;
+    const double2* val;      // the entry of A_k
+    const double2* valg;     // gamma_k times its conjugate (the A_k^dag factor of the dissipator)
+    int nnz;                // over all jump operators
+    // Frobenius norms for the bound of ||L(t) w||: ||K0||, (||Xs_p|| + ||Xt_p||), sum_k |gamma_k| ||A_k||^2
+    double nK0, nX[4], nD;
+};
+
+struct HilbertParams {
+    const HilbertSys* systems;  // device table, n_sys entries
+    const int* traj_sys;     // n_traj
+    int N, n_sub, n_out, nl_max;  // nl_max: most jump operators of any system (sizes the LDS work matrices)
+    double ta, dt;
+    const double2* rho0;     // N*N
+    const double2* ovec;     // n_out*N*N: ovec[k][i*N+j] = O_k[j][i]
+    const int* wbeg;         // per trajectory, as SweepParams
+    const int* wend;
+    const long long* woff;
+    const int* ev_start;     // n_traj+1
+    const int4* ev;          // (step, after?1:0, operator index, kind), sorted per trajectory, same slot in array order
+    const double2* mto;      // MTO operators, N*N each
+    double2* out;
+    int csr_lds;             // > 0: bytes of LDS for the nonzero lists (the largest system's, hilbert_csr_bytes), read
+                             //   from LDS; 0: a system's lists exceed HB_CSR_LDS, all are read from global memory
+};
+size_t hilbert_csr_bytes(int N, int n_lind, int nnz);  // LDS bytes of one system's nonzero lists (a multiple of 16)
+hipError_t launch_hilbert(int n_traj, const HilbertParams& p, hipStream_t s);
 
 // launchers (defined in the .hip translation units)
 hipError_t launch_dressed(int N, const DressedParams& p, hipStream_t s);

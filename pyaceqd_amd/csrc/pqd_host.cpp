@@ -126,9 +126,11 @@ void matmul_sq(int n, const cd* A, const cd* B, cd* Cm) {
     std::copy(t.begin(), t.end(), Cm);
 }
 
-int check_system(const pqd_system* sys) {
+// max_dim: 6 wherever N^2 x N^2 superoperators are built; HB_NMAX for a plan without PT (lind_hilbert.hip)
+int check_system(const pqd_system* sys, int max_dim = 6) {
     if (!sys) return fail(PQD_ERR_ARG, "system is NULL");
-    if (sys->dim < 2 || sys->dim > 6) return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [2, 6]", sys->dim);
+    if (sys->dim < 2 || sys->dim > max_dim)
+        return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [2, %d]", sys->dim, max_dim);
     if (!sys->H0) return fail(PQD_ERR_ARG, "H0 is NULL");
     if (!(sys->hbar > 0)) return fail(PQD_ERR_ARG, "hbar must be > 0");
     if (sys->n_lind < 0 || (sys->n_lind > 0 && (!sys->lind_ops || !sys->lind_rates)))
@@ -290,6 +292,13 @@ struct pqd_plan {
     DevBuf<int4> ev, units;
     FreePropParams fp{};
     SweepParams sp{};
+    // Hilbert-space path (lind_hilbert.hip): N x N operators per system, jump operators as nonzero lists by rows; the
+    // plan's M, F, W, blocks, trunks and superoperators stay empty
+    bool hilbert = false;
+    HilbertParams hp{};
+    DevBuf<HilbertSys> hb_systab;
+    DevBuf<double2> hb_K0, hb_Xs, hb_Xt, hb_val, hb_valg;
+    DevBuf<int> hb_row, hb_col;
     int64_t out_len = 0;
     int n_out = 0;
     double t_start = 0.0, dt = 0.0;
@@ -462,7 +471,7 @@ void pqd_pt_destroy(pqd_pt* pt) { delete pt; }
 struct PlanEnv {
     int split, msplit, ms_tb, ms_ptm, fp4, fpm, pt_mode, cmul3, trpre, bt, colbig, trunk, quad, qpw, qcg, qprio, win,
         rowpair, ablate;
-    bool ms_l2, split_ow, split_gran, split_xcd, sweep_lean, pt_mode_set, fuse, branch, idle, unitbal, split_l2;
+    bool ms_l2, split_ow, split_gran, split_xcd, sweep_lean, pt_mode_set, fuse, branch, idle, unitbal, split_l2, hilbert;
     unsigned split_spin;
 };
 
@@ -502,6 +511,7 @@ static PlanEnv read_plan_env() {
     const char* spin = getenv("PQD_SPLIT_SPIN");
     v.split_spin = spin ? (unsigned)strtoul(spin, nullptr, 10) : (1u << 22);  // polls before a split wait times out (~0.1 s)
     v.split_l2 = num("PQD_SPLIT_L2", 1) != 0;   // split exchange lines kept in L2 (0: sc1 stores)
+    v.hilbert = num("PQD_HILBERT", 0) == 1;     // 1: no-PT plans of dim <= 6 run the Hilbert-space kernel too (dim > 6 always)
     return v;
 }
 
@@ -872,8 +882,11 @@ static int check_plan_args(pqd_ctx* ctx, int32_t n_sys, const pqd_system* system
     if (n_sys > 1 && !traj_sys) return fail(PQD_ERR_ARG, "traj_sys is NULL with n_sys > 1");
     int rc = 0;
     for (int k = 0; k < n_sys; ++k) {
-        if ((rc = check_system(&systems[k]))) return rc;
+        if ((rc = check_system(&systems[k], pt ? 6 : HB_NMAX))) return rc;
         if (systems[k].dim != systems[0].dim) return fail(PQD_ERR_ARG, "system %d: dim %d != %d", k, systems[k].dim, systems[0].dim);
+        if (systems[k].dim > 6 && systems[k].n_lind > HB_LMAX)  // dim > 6 runs in Hilbert space only (lind_hilbert.hip)
+            return fail(PQD_ERR_UNSUPPORTED, "system %d: n_lind %d not in [0, %d] at dim %d > 6", k, systems[k].n_lind,
+                        HB_LMAX, systems[k].dim);
     }
     const pqd_system* sys = systems;
     for (int t = 0; t < tr->n_traj; ++t)
@@ -1471,6 +1484,155 @@ static int build_msplit_tables(pqd_plan* P, const PathChoice& pc, const std::vec
     return PQD_OK;
 }
 
+// A plan on the Hilbert-space path (lind_hilbert.hip): per system K0 = -(i/hbar) H0 - 1/2 sum_k gamma_k A_k^dag A_k,
+// the channel operators scaled by -i/hbar, the jump operators' nonzeros by rows and the Frobenius norms of the kernel's
+// step bound; MTOs as the N x N operators they are, in array order inside a (trajectory, step, phase) slot. No
+// superoperator, block, trunk or free propagator is built. Refuses a system whose bound needs more than HB_SMAX
+// Taylor factors per sub-step (a non-finite bound passes: the run then ends in PQD_ERR_NUMERIC).
+static int setup_hilbert(pqd_plan* P, const pqd_system* systems, const std::vector<int>& tsys, const pqd_grid* grid,
+                         const pqd_c128* rho0, const pqd_c128* out_ops, const pqd_traj* tr, hipStream_t s) {
+    const int N = systems->dim, NN = N * N, n_sys = P->n_sys, n_out = P->n_out, n_w = std::max(1, P->n_traj);
+    const double w = 0.5 * grid->dt / grid->n_sub;
+    std::vector<cd> k0((size_t)n_sys * NN), xs, xt, sm, val, valg;
+    std::vector<int> row, col;
+    std::vector<HilbertSys> tab(n_sys);
+    std::vector<size_t> oX(n_sys), oM(n_sys), oR(n_sys), oV(n_sys);
+    auto fro = [&](const cd* A) { double q = 0; for (int e = 0; e < NN; ++e) q += std::norm(A[e]); return std::sqrt(q); };
+    int nl_max = 0;
+    size_t csr_max = 0;
+    for (int k = 0; k < n_sys; ++k) {
+        const pqd_system& y = systems[k];
+        HilbertSys& h = tab[k];
+        const cd mih(0.0, -1.0 / y.hbar);
+        cd* K0 = k0.data() + (size_t)k * NN;
+        for (int e = 0; e < NN; ++e) K0[e] = mih * C(y.H0)[e];
+        h.n_lind = y.n_lind;
+        h.nD = 0.0;
+        oR[k] = row.size();
+        oV[k] = val.size();
+        for (int q = 0; q < y.n_lind; ++q) {
+            const cd* A = C(y.lind_ops) + (size_t)q * NN;
+            const double g = y.lind_rates[q];
+            for (int i = 0; i < N; ++i)
+                for (int j = 0; j < N; ++j) {
+                    cd a = 0;
+                    for (int m = 0; m < N; ++m) a += std::conj(A[m * N + i]) * A[m * N + j];
+                    K0[i * N + j] -= 0.5 * g * a;
+                }
+            const double nA = fro(A);
+            h.nD += std::fabs(g) * nA * nA;
+            for (int i = 0; i < N; ++i) {
+                row.push_back((int)(val.size() - oV[k]));
+                for (int j = 0; j < N; ++j)
+                    if (A[i * N + j] != cd(0.0)) {
+                        col.push_back(j);
+                        val.push_back(A[i * N + j]);
+                        valg.push_back(g * std::conj(A[i * N + j]));
+                    }
+            }
+            row.push_back((int)(val.size() - oV[k]));
+        }
+        h.nnz = (int)(val.size() - oV[k]);
+        h.nK0 = fro(K0);
+        h.n_chan = y.n_chan;
+        h.n_samples = std::max(1, y.n_samples);
+        h.s_t0 = y.sample_t0;
+        h.s_dt = y.n_chan > 0 ? y.sample_dt : 1.0;
+        oX[k] = xs.size();
+        oM[k] = sm.size();
+        double bound = h.nK0;
+        for (int p = 0; p < y.n_chan; ++p) {
+            const cd* X = C(y.chan_ops) + (size_t)p * NN;
+            for (int i = 0; i < N; ++i)
+                for (int j = 0; j < N; ++j) {
+                    xs.push_back(mih * X[i * N + j]);
+                    xt.push_back(mih * std::conj(X[j * N + i]));
+                }
+            h.nX[p] = fro(xs.data() + xs.size() - NN) + fro(xt.data() + xt.size() - NN);
+            const cd* f = C(y.chan_samples) + (size_t)p * y.n_samples;
+            double fmax = 0.0;
+            for (int q = 0; q < y.n_samples; ++q) fmax = std::max(fmax, std::abs(f[q]));  // a NaN sample is skipped here
+            bound += fmax * h.nX[p];
+            sm.insert(sm.end(), f, f + y.n_samples);
+        }
+        const double theta = w * (2.0 * bound + h.nD);
+        if (std::isfinite(theta) && theta > (double)HB_SMAX)
+            return fail(PQD_ERR_UNSUPPORTED, "system %d: the norm bound of L w is %.3g, above %d Taylor factors per "
+                        "sub-step (lower dt or raise n_sub)", k, theta, HB_SMAX);
+        nl_max = std::max(nl_max, y.n_lind);
+        csr_max = std::max(csr_max, hilbert_csr_bytes(N, y.n_lind, h.nnz));
+    }
+    if (xs.empty()) { xs.assign(1, 0.0); xt.assign(1, 0.0); }
+    if (sm.empty()) sm.assign(1, 0.0);
+    if (val.empty()) { val.assign(1, 0.0); valg.assign(1, 0.0); col.assign(1, 0); }
+    if (row.empty()) row.assign(1, 0);
+    HIPCHK(P->hb_K0.upload(reinterpret_cast<double2*>(k0.data()), k0.size(), s));
+    HIPCHK(P->hb_Xs.upload(reinterpret_cast<double2*>(xs.data()), xs.size(), s));
+    HIPCHK(P->hb_Xt.upload(reinterpret_cast<double2*>(xt.data()), xt.size(), s));
+    HIPCHK(P->samples.upload(reinterpret_cast<double2*>(sm.data()), sm.size(), s));
+    HIPCHK(P->hb_val.upload(reinterpret_cast<double2*>(val.data()), val.size(), s));
+    HIPCHK(P->hb_valg.upload(reinterpret_cast<double2*>(valg.data()), valg.size(), s));
+    HIPCHK(P->hb_col.upload(col.data(), col.size(), s));
+    HIPCHK(P->hb_row.upload(row.data(), row.size(), s));
+    for (int k = 0; k < n_sys; ++k) {
+        tab[k].K0 = P->hb_K0.p + (size_t)k * NN;
+        tab[k].Xs = P->hb_Xs.p + oX[k];
+        tab[k].Xt = P->hb_Xt.p + oX[k];
+        tab[k].samples = P->samples.p + oM[k];
+        tab[k].rowptr = P->hb_row.p + oR[k];
+        tab[k].col = P->hb_col.p + oV[k];
+        tab[k].val = P->hb_val.p + oV[k];
+        tab[k].valg = P->hb_valg.p + oV[k];
+    }
+    HIPCHK(P->hb_systab.upload(tab.data(), tab.size(), s));
+    HIPCHK(P->traj_sys.upload(tsys.data(), tsys.size(), s));
+
+    // MTO events per trajectory, stable-sorted by (step, phase): (step, 1 after the output / 0 before, operator, kind)
+    std::vector<std::vector<int>> per(tr->n_traj);
+    for (int q = 0; q < tr->n_mto; ++q) per[tr->mto_traj[q]].push_back(q);
+    std::vector<int> ev_start(tr->n_traj + 1, 0);
+    std::vector<int4> evs;
+    for (int t = 0; t < tr->n_traj; ++t) {
+        auto& v = per[t];
+        auto key = [&](int q) { return 2 * tr->mto_step[q] + (tr->mto_before[q] ? 0 : 1); };
+        std::stable_sort(v.begin(), v.end(), [&](int a, int b) { return key(a) < key(b); });
+        ev_start[t] = (int)evs.size();
+        for (int q : v) evs.push_back(make_int4(key(q) >> 1, key(q) & 1, q, tr->mto_kind[q]));
+        P->traj_steps += tr->out_end[t] + 1;
+    }
+    ev_start[tr->n_traj] = (int)evs.size();
+    if (evs.empty()) evs.push_back(make_int4(-1, -1, 0, 0));
+    HIPCHK(P->ev.upload(evs.data(), evs.size(), s));
+    HIPCHK(P->ev_start.upload(ev_start.data(), ev_start.size(), s));
+    if (tr->n_mto > 0)
+        HIPCHK(P->sop.upload(reinterpret_cast<const double2*>(tr->mto_ops), (size_t)tr->n_mto * NN, s));
+    std::vector<cd> ov((size_t)n_out * NN);
+    for (int k = 0; k < n_out; ++k)
+        for (int i = 0; i < N; ++i)
+            for (int j = 0; j < N; ++j) ov[(size_t)k * NN + i * N + j] = C(out_ops)[(size_t)k * NN + j * N + i];
+    HIPCHK(P->ovec.upload(reinterpret_cast<double2*>(ov.data()), ov.size(), s));
+    HIPCHK(P->rho0.upload(reinterpret_cast<const double2*>(rho0), NN, s));
+    HIPCHK(P->wbeg.upload(tr->out_begin, n_w, s));
+    HIPCHK(P->wend.upload(tr->out_end, n_w, s));
+    HIPCHK(P->woff.upload(reinterpret_cast<const long long*>(tr->out_offset), n_w, s));
+    HIPCHK(P->out.alloc(std::max<int64_t>(1, P->out_len)));
+    HIPCHK(hipMemsetAsync(P->out.p, 0, std::max<int64_t>(1, P->out_len) * sizeof(double2), s));
+    HIPCHK(P->flags.alloc(4));
+    HIPCHK(hipMemsetAsync(P->flags.p, 0, 4 * sizeof(unsigned), s));
+
+    HilbertParams& hp = P->hp;
+    hp.systems = P->hb_systab.p; hp.traj_sys = P->traj_sys.p;
+    hp.N = N; hp.n_sub = grid->n_sub; hp.n_out = n_out; hp.nl_max = nl_max;
+    hp.ta = grid->ta; hp.dt = grid->dt;
+    hp.rho0 = P->rho0.p; hp.ovec = P->ovec.p; hp.wbeg = P->wbeg.p; hp.wend = P->wend.p; hp.woff = P->woff.p;
+    hp.ev_start = P->ev_start.p; hp.ev = P->ev.p; hp.mto = P->sop.p; hp.out = P->out.p;
+    hp.csr_lds = csr_max <= (size_t)HB_CSR_LDS ? (int)csr_max : 0;
+    P->BT = 1;
+    P->n_blocks = P->n_traj;
+    HIPCHK(hipStreamSynchronize(s));  // the uploads read host vectors of this frame
+    return PQD_OK;
+}
+
 int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const int32_t* traj_sys,
                           const pqd_grid* grid, const pqd_pt* pt, const int32_t* sched, const pqd_c128* rho0,
                           int32_t n_out, const pqd_c128* out_ops, const pqd_traj* tr, int64_t out_len,
@@ -1498,6 +1660,16 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
 
     std::vector<int> tsys(std::max(1, n_traj), 0);
     for (int t = 0; t < n_traj; ++t) tsys[t] = traj_sys ? traj_sys[t] : 0;
+    // without a PT, dim > 6 runs in Hilbert space (nothing else holds it); PQD_HILBERT=1 sends dim <= 6 there too,
+    // where the systems keep to the kernel's limit of jump operators
+    bool hb_fits = !pt;
+    for (int k = 0; k < n_sys; ++k) hb_fits = hb_fits && systems[k].n_lind <= HB_LMAX;
+    if (!pt && (N > 6 || (env.hilbert && hb_fits))) {
+        P->hilbert = true;
+        if ((rc = setup_hilbert(P, systems, tsys, grid, rho0, out_ops, tr, s))) return rc;
+        *out = guard.release();
+        return PQD_OK;
+    }
     MtoEvents E = compose_mtos(N, tr);
     if ((rc = upload_inputs(P, systems, tsys, E, rho0, out_ops, tr, s))) return rc;
 
@@ -1545,6 +1717,15 @@ int pqd_plan_execute(pqd_plan* P, int32_t rebuild_free) {
     }
     hipEvent_t* e = P->ring + 3 * P->ev_head;
     HIPCHK(hipEventRecord(e[0], s));
+    if (P->hilbert) {  // one kernel, no free propagators to rebuild
+        HIPCHK(hipEventRecord(e[1], s));
+        HIPCHK(launch_hilbert(P->n_traj, P->hp, s));
+        HIPCHK(hipEventRecord(e[2], s));
+        P->ev_head = (P->ev_head + 1) % pqd_plan::RING;
+        P->ev_count++;
+        P->execs++;
+        return PQD_OK;
+    }
     if (rebuild_free && P->n_steps > 0) {
         HIPCHK(launch_free_prop(P->N2, P->fp, s));
         if (P->sp.fuse) HIPCHK(launch_fuse_steps(P->N2, P->fu, s));
@@ -1732,7 +1913,7 @@ int pqd_plan_sweep_lean(const pqd_plan* P, int32_t* on) {
 }
 
 static int plan_path(const pqd_plan* P) {
-    return P->nopt ? PQD_PATH_NOPT : P->split ? PQD_PATH_SPLIT : P->msplit ? PQD_PATH_MSPLIT
+    return P->hilbert ? PQD_PATH_HILBERT : P->nopt ? PQD_PATH_NOPT : P->split ? PQD_PATH_SPLIT : P->msplit ? PQD_PATH_MSPLIT
          : P->quad ? PQD_PATH_QUAD : PQD_PATH_BATCHED;
 }
 
@@ -1780,6 +1961,7 @@ int pqd_plan_timing(pqd_plan* P, double* ms_free, double* ms_sweep, int32_t* n, 
         HIPCHK(hipEventElapsedTime(&b, e[1], e[2]));
         f += a; w += b;
     }
+    if (P->hilbert) f = 0.0;  // no free-propagator build on this path (the two events are back to back)
     if (ms_free) *ms_free = k ? f / k : 0.0;
     if (ms_sweep) *ms_sweep = k ? w / k : 0.0;
     if (n) *n = k;

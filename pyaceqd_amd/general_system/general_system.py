@@ -292,6 +292,16 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
     if dim is None:
         dim = 2  # "assuming TLS" (:19)
     mat = lambda s: opgrammar.to_matrix(s, dim)  # noqa: E731
+    if dim > 6:
+        # above dim 6 only the propagation without PT exists (the Hilbert-space kernel, dim <= 24): everything that
+        # builds N^2 x N^2 superoperators stops at 6. Refused here, before a PT is generated or read
+        from .._lib import HILBERT_MAX_DIM
+        for name, on in (("phonons=True", phonons), ("calc_dynmap", calc_dynmap), ("get_M_t", get_M_t is not None),
+                         ("dressedstates", dressedstates)):
+            if on:
+                raise NotImplementedError(f"{name} needs dim <= 6, this system has dim {dim} (without it a system "
+                                          f"of dim <= {HILBERT_MAX_DIM} propagates)")
+
     def hamiltonian(ops):
         H = np.zeros((dim, dim), dtype=complex)
         for s in (ops or []):
