@@ -30,6 +30,54 @@ def random_system(N, n_chan=2, n_lind=2, seed=0, n_steps=20, dt=0.1, ta=0.0, n_s
     return sysd, Grid(ta, dt, n_steps, n_sub)
 
 
+def sparse_jump_ops(N, n_lind, seed):
+    """(rate, A) with the nonzero structures of the reference models, cycled over k: diagonal, a single entry,
+    strictly upper triangular with about N entries, N // 2 occupied rows (chosen at random) of one or two entries;
+    from n_lind = 5 on, operator 4 is entirely zero (all its row offsets equal). Rates as random_system's."""
+    rng = np.random.default_rng(seed)
+    val = lambda: complex(rng.normal(), rng.normal())  # noqa: E731
+    ops = []
+    for k in range(n_lind):
+        A = np.zeros((N, N), dtype=complex)
+        kind = k % 4
+        if k == 4:
+            pass
+        elif kind == 0:
+            for i in range(N):
+                A[i, i] = val()
+        elif kind == 1:
+            A[int(rng.integers(N)), int(rng.integers(N))] = val()
+        elif kind == 2:
+            for i in range(N - 1):
+                A[i, i + 1] = val()
+            A[0, N - 1] = val()
+        else:
+            for i in rng.choice(N, size=N // 2, replace=False):
+                for j in rng.choice(N, size=int(rng.integers(1, 3)), replace=False):
+                    A[i, j] = val()
+        ops.append((0.05 * (k + 1), A))
+    return ops
+
+
+def offgrid_channels(sysd, grid, cover=(0.23, 0.78), sdt=0.0137 * np.pi, floor=0.3):
+    """Replace the samples of every channel of `sysd` (in place; returned for convenience) by samples on a raster
+    incommensurate with grid.dt that spans only the `cover` fraction of the run: sub-step midpoints fall between
+    samples (interpolation weights all over (0, 1)), before the first and after the last one (clamping). The envelope
+    is floor + (1 - floor) 4 x (1 - x) over the samples, so both end values are `floor`: non-zero makes the clamped
+    values visible, floor = 0 gives exact zeros at both ends (pulse windows). Sets sample_t0 and sample_dt."""
+    T = grid.n_steps * grid.dt
+    t_lo, t_hi = grid.ta + cover[0] * T, grid.ta + cover[1] * T
+    ns = max(1, int((t_hi - t_lo) / sdt))
+    k = np.arange(ns)
+    x = k / max(1, ns - 1)
+    env = floor + (1.0 - floor) * 4.0 * x * (1.0 - x)
+    tt = t_lo + sdt * k
+    sysd.channels = [(X, (env * np.exp(1j * (c + 1) * tt)).astype(complex)) for c, (X, _) in enumerate(sysd.channels)]
+    sysd.sample_t0 = float(t_lo)
+    sysd.sample_dt = float(sdt)
+    return sysd
+
+
 def random_rho(N, seed=1):
     rng = np.random.default_rng(seed)
     A = rng.normal(size=(N, N)) + 1j * rng.normal(size=(N, N))
