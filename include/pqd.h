@@ -150,7 +150,17 @@ int pqd_dressed_states(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, c
                        double* evals,         /* n_sys*(n_steps+1)*N        or NULL */
                        pqd_c128* evecs,       /* n_sys*(n_steps+1)*N*N, [s][n][j][i] = component i of eigenvector j, or NULL */
                        double* occ);          /* n_sys*(n_steps+1)*N, needs rho; or NULL */
-/* duration (ms, HIP events on the context stream) of the kernel of the context's last pqd_dressed_states call */
+/* Dressed states of the cavity and sensor models: pqd_dressed_states for systems of equal dim in [7, 24]
+ * (PQD_ERR_UNSUPPORTED "dim %d not in [7, 24]" otherwise), with its signature, layouts, argument checks, order, norm,
+ * phase and occupation rule. Serves tls_photons_dressed_states (two_level_system/tls.py:207-212),
+ * biexciton_photons_dressed_states and biexciton_photons_extended_dressed_states (four_level_system/linear.py:105-109,
+ * 157-159) and dressed_states(system, dim, ...) for any model of that size (general_dressed_states.py:26-44). The
+ * solver is a round-robin Jacobi in LDS (csrc/dressed_wide.hip) with the same stop rule, 40 sweeps at most;
+ * PQD_ERR_NUMERIC (outputs still copied) when an H entry is not finite or a problem did not converge in them. */
+int pqd_dressed_states_wide(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const pqd_grid* grid,
+                            const pqd_c128* rho, double* evals, pqd_c128* evecs, double* occ);
+/* duration (ms, HIP events on the context stream) of the kernel of the context's last pqd_dressed_states or
+ * pqd_dressed_states_wide call, whichever ran last */
 int pqd_dressed_timing(pqd_ctx* ctx, double* ms_kernel);
 
 /* one-shot: upload, propagate, download. pt may be NULL (no phonons); sched[n_steps] selects the

@@ -81,6 +81,8 @@ _SIGS = {
     "pqd_free_propagators": ([C.c_void_p, C.POINTER(pqd_system), C.POINTER(pqd_grid), P_C128], C.c_int),
     "pqd_dressed_states": ([C.c_void_p, C.c_int32, C.POINTER(pqd_system), C.POINTER(pqd_grid), P_C128, P_F64, P_C128,
                             P_F64], C.c_int),
+    "pqd_dressed_states_wide": ([C.c_void_p, C.c_int32, C.POINTER(pqd_system), C.POINTER(pqd_grid), P_C128, P_F64,
+                                 P_C128, P_F64], C.c_int),
     "pqd_dressed_timing": ([C.c_void_p, P_F64], C.c_int),
     "pqd_propagate": ([C.c_void_p, C.POINTER(pqd_system), C.POINTER(pqd_grid), C.c_void_p, P_I32, P_C128,
                        C.c_int32, P_C128, C.POINTER(pqd_traj), P_C128, C.c_int64], C.c_int),

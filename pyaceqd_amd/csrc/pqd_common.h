@@ -351,7 +351,8 @@ size_t hilbert_csr_bytes(int N, int n_lind, int nnz);  // LDS bytes of one syste
 hipError_t launch_hilbert(int n_traj, const HilbertParams& p, hipStream_t s);
 
 // launchers (defined in the .hip translation units)
-hipError_t launch_dressed(int N, const DressedParams& p, hipStream_t s);
+hipError_t launch_dressed(int N, const DressedParams& p, hipStream_t s);       // N = 2..6 (dressed.hip)
+hipError_t launch_dressed_wide(int N, const DressedParams& p, hipStream_t s);  // N = 7..24 (dressed_wide.hip)
 struct FuseParams {          // F(m) = M_a(m) M_b(m-1) (1 <= m < n_steps), W(m) = ovec . M_b(m-1) (1 <= m <= n_steps)
     const double2* M;
     double2* F;

@@ -546,14 +546,17 @@ int pqd_free_propagators(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* gr
 
 // Dressed states: H0, the channel operators and the samples of every system go up as they are (no generators: the
 // kernel diagonalises H itself), one kernel solves every (system, output time), the requested outputs come back.
-int pqd_dressed_states(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const pqd_grid* grid,
-                       const pqd_c128* rho, double* evals, pqd_c128* evecs, double* occ) {
+// The two entry points differ in the dim range, the kernel's launcher and the sweep limit their messages name.
+typedef hipError_t (*dressed_launcher)(int, const DressedParams&, hipStream_t);
+static int dressed_states_impl(const char* who, int lo, int hi, dressed_launcher launch, int max_sweeps, pqd_ctx* ctx,
+                               int32_t n_sys, const pqd_system* systems, const pqd_grid* grid, const pqd_c128* rho,
+                               double* evals, pqd_c128* evecs, double* occ) {
     if (!evals && !evecs && !occ) return fail(PQD_ERR_ARG, "no output requested (evals, evecs and occ are all NULL)");
     if (occ && !rho) return fail(PQD_ERR_ARG, "occ needs rho");
     if (n_sys < 1 || !systems) return fail(PQD_ERR_ARG, "need at least one system");
     for (int k = 0; k < n_sys; ++k) {  // check_system without the Lindblad terms and hbar, which H(t) does not hold
         const pqd_system& y = systems[k];
-        if (y.dim < 2 || y.dim > 6) return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [2, 6]", y.dim);
+        if (y.dim < lo || y.dim > hi) return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [%d, %d]", y.dim, lo, hi);
         if (!y.H0) return fail(PQD_ERR_ARG, "H0 is NULL");
         if (y.n_chan < 0 || y.n_chan > 4) return fail(PQD_ERR_UNSUPPORTED, "n_chan %d not in [0, 4]", y.n_chan);
         if (y.n_chan > 0 && (!y.chan_ops || !y.chan_samples || y.n_samples < 1 || !(y.sample_dt > 0)))
@@ -618,7 +621,7 @@ int pqd_dressed_states(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, c
     HIPCHK(hipEventCreate(&e0));
     hipError_t he = hipEventCreate(&e1);
     if (he == hipSuccess) he = hipEventRecord(e0, s);
-    if (he == hipSuccess) he = launch_dressed(N, dp, s);
+    if (he == hipSuccess) he = launch(N, dp, s);
     if (he == hipSuccess) he = hipEventRecord(e1, s);
     unsigned hf = 0;
     if (he == hipSuccess && evals)
@@ -633,11 +636,25 @@ int pqd_dressed_states(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, c
     if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (he != hipSuccess) return fail(PQD_ERR_HIP, "pqd_dressed_states: %s", hipGetErrorString(he));
+    if (he != hipSuccess) return fail(PQD_ERR_HIP, "%s: %s", who, hipGetErrorString(he));
     ctx->dressed_ms = ms;
-    if (hf & 1u) return fail(PQD_ERR_NUMERIC, "pqd_dressed_states: H(t) holds a non-finite entry");
-    if (hf & 2u) return fail(PQD_ERR_NUMERIC, "pqd_dressed_states: a problem did not converge in 30 Jacobi sweeps");
+    if (hf & 1u) return fail(PQD_ERR_NUMERIC, "%s: H(t) holds a non-finite entry", who);
+    if (hf & 2u)
+        return fail(PQD_ERR_NUMERIC, "%s: a problem did not converge in %d Jacobi sweeps", who, max_sweeps);
     return PQD_OK;
+}
+
+int pqd_dressed_states(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const pqd_grid* grid,
+                       const pqd_c128* rho, double* evals, pqd_c128* evecs, double* occ) {
+    return dressed_states_impl("pqd_dressed_states", 2, 6, launch_dressed, 30, ctx, n_sys, systems, grid, rho, evals,
+                               evecs, occ);
+}
+
+// The cavity and sensor models (dim 7..24): the same call on the LDS-resident round-robin solver (dressed_wide.hip)
+int pqd_dressed_states_wide(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const pqd_grid* grid,
+                            const pqd_c128* rho, double* evals, pqd_c128* evecs, double* occ) {
+    return dressed_states_impl("pqd_dressed_states_wide", 7, 24, launch_dressed_wide, 40, ctx, n_sys, systems, grid,
+                               rho, evals, evecs, occ);
 }
 
 int pqd_dressed_timing(pqd_ctx* ctx, double* ms_kernel) {

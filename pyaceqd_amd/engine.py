@@ -340,12 +340,13 @@ def free_propagators(system: System, grid: Grid, ctx=None):
     return M[: 2 * grid.n_steps]
 
 
-DRESSED_LAUNCHES = 0  # pqd_dressed_states calls issued by this process (tests count launches with it)
+DRESSED_LAUNCHES = 0  # pqd_dressed_states[_wide] calls issued by this process (tests count launches with it)
 
 
 def dressed_states(system_or_systems, grid: Grid, rho=None, want_vectors=True, ctx=None):
-    """Dressed states of every system at every output time of `grid` in one launch (pqd_dressed_states): the
-    eigenpairs of H(t_n) = H0 + sum_p (f_p(t_n) X_p + h.c.), Lindblad terms and n_sub ignored.
+    """Dressed states of every system at every output time of `grid` in one launch (pqd_dressed_states for dim <= 6,
+    pqd_dressed_states_wide for dim 7..24): the eigenpairs of H(t_n) = H0 + sum_p (f_p(t_n) X_p + h.c.), Lindblad
+    terms and n_sub ignored.
 
     Returns (evals, evecs, occ), each with leading axes (n_sys, n_steps + 1), or (n_steps + 1,) when a single System
     (not a list) was passed: evals (..., N) ascending; evecs (..., N, N) with evecs[..., j, i] = component i of
@@ -374,8 +375,10 @@ def dressed_states(system_or_systems, grid: Grid, rho=None, want_vectors=True, c
         sc = (_lib.pqd_system * n_sys)(*[c for c, _ in convs])
         gc = grid.to_c()
         DRESSED_LAUNCHES += 1
-        _lib.check(_lib.lib().pqd_dressed_states(ctx.handle, n_sys, sc, C.byref(gc), _lib.cptr(r), _lib.fptr(evals),
-                                                 _lib.cptr(evecs), _lib.fptr(occ)))
+        # N <= 6: a column per lane in registers (dressed.hip); above: the LDS-resident solver, N <= 24 (dressed_wide.hip)
+        call = _lib.lib().pqd_dressed_states if N <= 6 else _lib.lib().pqd_dressed_states_wide
+        _lib.check(call(ctx.handle, n_sys, sc, C.byref(gc), _lib.cptr(r), _lib.fptr(evals), _lib.cptr(evecs),
+                        _lib.fptr(occ)))
     if single:
         return evals[0], None if evecs is None else evecs[0], None if occ is None else occ[0]
     return evals, evecs, occ

@@ -13,7 +13,8 @@ from .. import constants
 hbar = constants.hbar
 temp_dir = constants.temp_dir
 
-_FWD = ("trajectories", "n_sub", "device", "rho0", "get_M_t", "pulse_sampling", "trapz", "dressed_rho")
+_FWD = ("trajectories", "n_sub", "device", "rho0", "get_M_t", "pulse_sampling", "trapz", "dressed_rho",
+        "lower_only")
 
 
 def biexciton_ops(delta_xy=0, shift_x=True, coupl_xy=0, delta_b=4, gamma_e=1/100, gamma_b=None, lindblad=False,
@@ -246,3 +247,26 @@ def biexciton_dressed_states(t_start, t_end, *pulses, plot=True, t_lim=None, e_l
     return dressed_states(biexciton, 4, t_start, t_end, *pulses, filename=filename, t_lim=t_lim, e_lim=e_lim,
                           plot=plot, firstonly=firstonly, colors=colors, visible_states=visible_states,
                           return_eigenvectors=return_eigenvectors, **options)
+
+
+def biexciton_photons_dressed_states(t_start, t_end, *pulses, plot=True, t_lim=None, e_lim=None,
+                                     filename="biexciton_photons_dressed", firstonly=False, visible_states=None,
+                                     **options):
+    """Dressed states of the biexciton in two cavity modes (pyaceqd/four_level_system/linear.py:105-109), dim
+    [4, n_phot1 + 1, n_phot2 + 1]: the reference's tuple, equally spaced colours. The reference needs n_phot1 and
+    n_phot2 among the options (KeyError otherwise); absent, biexciton_photons' defaults (1, 1: dim 16) are taken."""
+    from ..general_system.general_dressed_states import dressed_states
+    dim = [4, options.get("n_phot1", 1) + 1, options.get("n_phot2", 1) + 1]
+    return dressed_states(biexciton_photons, dim, t_start, t_end, *pulses, filename=filename, plot=plot, t_lim=t_lim,
+                          e_lim=e_lim, firstonly=firstonly, colors=None, visible_states=visible_states, **options)
+
+
+def biexciton_photons_extended_dressed_states(t_start, t_end, *pulses, plot=True, t_lim=None, e_lim=None,
+                                              filename="biexciton_photons_extended_dressed", firstonly=False,
+                                              visible_states=None, **options):
+    """Dressed states of the 18-state biexciton-cavity model with two excitations in total
+    (pyaceqd/four_level_system/linear.py:157-159): the reference's tuple, equally spaced colours."""
+    from ..general_system.general_dressed_states import dressed_states
+    return dressed_states(biexciton_photons_extended, 18, t_start, t_end, *pulses, filename=filename, t_lim=t_lim,
+                          e_lim=e_lim, plot=plot, firstonly=firstonly, colors=None, visible_states=visible_states,
+                          **options)

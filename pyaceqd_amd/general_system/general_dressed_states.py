@@ -17,6 +17,9 @@ import numpy as np
 
 from ..tools import basis_states, compose_dm, output_ops_dm
 
+WIDE_MAX_DIM = 24      # pqd_dressed_states_wide, and the propagation without a PT, stop here
+_PLAN_MAX_OPS = 256    # output operators one propagation call takes (pqd_host.cpp: "n_out ... not in [1, 256]")
+
 
 def hex_to_rgba(hex_code):
     """'#RRGGBB' or '#RRGGBBAA' -> (r, g, b, a) in 0..255; alpha 255 when absent"""
@@ -122,14 +125,21 @@ def dressed_states(system, dim, t_start, t_end, *pulses, plot=True, t_lim=None, 
 
     With trajectories=[{"pulses": (...)}, ...] (per-drive specs as system_ace_stream takes them): a list of tuples, one
     per spec, from two launches: one batched propagation and one dressed-state launch with the occupations evaluated
-    on the device."""
+    on the device.
+
+    prod(dim) in 7..24 (the cavity and sensor models) takes `_dressed_wide`: the same tuple(s) from the Hilbert-space
+    propagation and pqd_dressed_states_wide. Above 24: NotImplementedError."""
     n = int(np.prod(dim))
+    if n > WIDE_MAX_DIM:
+        raise NotImplementedError(f"dressed states need dim <= {WIDE_MAX_DIM}, this system has dim {n}")
     options["output_ops"] = output_ops_dm(dim)
     if colors is None:
         colors = select_equally_spaced_colors(n=n)
     common = dict(colors=colors, filename=filename, plot=plot, t_lim=t_lim, e_lim=e_lim,
                   visible_states=visible_states, return_eigenvectors=return_eigenvectors, print_states=print_states)
     specs = options.get("trajectories")
+    if n > 6:
+        return _dressed_wide(system, dim, n, t_start, t_end, pulses, specs, firstonly, no_pulse, options, common)
     if specs is None:
         _, rho = compose_dm(system(t_start, t_end, *pulses, **options), dim=n)
         options["dressedstates"] = True
@@ -148,3 +158,45 @@ def _dressed_batch(system, dim, n, t_start, t_end, pulses, specs, firstonly, no_
     runs = system(t_start, t_end, *([] if no_pulse else pulses), **opts)
     return [_dressed_states(dim=dim, data=data, rho=rho, _ds_occ=occ, **common)
             for (data, occ), rho in zip(runs, rhos)]
+
+
+def _propagate_dm(system, t_start, t_end, pulses, options):
+    """the propagation with output_ops_dm's n (n + 1) / 2 operators, in ceil(n (n + 1) / 512) calls on slices of the
+    operator list (one up to n = 22, two at 23 and 24), the rows reassembled into one table (per trajectory)"""
+    ops = options["output_ops"]
+    n_calls = -(-len(ops) // _PLAN_MAX_OPS)
+    if n_calls == 1:
+        return system(t_start, t_end, *pulses, **options)
+    size = -(-len(ops) // n_calls)
+    parts = [system(t_start, t_end, *pulses, **dict(options, output_ops=ops[k: k + size]))
+             for k in range(0, len(ops), size)]
+    if options.get("trajectories") is None:
+        return np.concatenate([parts[0]] + [q[1:] for q in parts[1:]])
+    return [np.concatenate([qs[0]] + [q[1:] for q in qs[1:]]) for qs in zip(*parts)]
+
+
+def _dressed_wide(system, dim, n, t_start, t_end, pulses, specs, firstonly, no_pulse, options, common):
+    """dim 7..24. `dressedstates=True` stays a dim <= 6 switch (the reference calls it internal to these functions);
+    H(t) comes from the model's own lowering instead (lower_only=True: no device, no PT), one System per spec, and
+    one dressed-state launch diagonalises all of them and evaluates the occupations against the propagated rho."""
+    from .. import _lib, engine
+    tables = _propagate_dm(system, t_start, t_end, pulses, options)
+    rhos = [compose_dm(r, dim=n)[1] for r in (tables if specs is not None else [tables])]
+    opts = dict(options, lower_only=True, firstonly=firstonly)
+    if specs is not None and no_pulse:
+        opts["trajectories"] = [dict(s, pulses=()) for s in specs]
+    low = system(t_start, t_end, *([] if no_pulse else pulses), **opts)
+    # one problem set per trajectory, with its density matrices (rows past a shorter trajectory's end stay 0)
+    rho_all = np.zeros((len(low.traj_sys), low.grid.n_steps + 1, n, n), dtype=complex)
+    for k, r in enumerate(rhos):
+        if r.shape != (low.n_t[k], n, n):
+            raise ValueError(f"trajectory {k}: rho has shape {r.shape}, expected {(low.n_t[k], n, n)}")
+        rho_all[k, :low.n_t[k]] = r
+    ev, vec, occ = engine.dressed_states([low.systems[i] for i in low.traj_sys], low.grid, rho=rho_all,
+                                         ctx=_lib.context(options.get("device")))
+    res = []
+    for k, rho in enumerate(rhos):
+        m = low.n_t[k]
+        tab = engine.dressed_table(low.grid.times[:m], ev[k][:m], vec[k][:m])
+        res.append(_dressed_states(dim=dim, data=tab, rho=rho, _ds_occ=occ[k][:m], **common))
+    return res if specs is not None else res[0]

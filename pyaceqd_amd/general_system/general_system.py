@@ -23,6 +23,7 @@ choice is a documented switch):
 """
 import os
 import warnings
+from collections import namedtuple
 
 import numpy as np
 
@@ -230,6 +231,9 @@ def _write_J(J_to_file, ae, factor_ah, J_file):
     ptgen.write_J(J_to_file, J, 0.0, 15.0, 2000)
 
 
+Lowered = namedtuple("Lowered", "systems traj_sys grid n_t")  # system_ace_stream(..., lower_only=True)
+
+
 def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.48, ae=3.0, temperature=1,
                       verbose=False, temp_dir=temp_dir, pt_file=None, suffix="", multitime_op=None,
                       pulse_file_x=None, pulse_file_y=None, system_prefix="", threshold="10", threshold_ratio="0.3",
@@ -238,7 +242,7 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
                       prepare_only=False, LO_params=None, dressedstates=False, rf_op=None, rf_file=None,
                       firstonly=False, J_to_file=None, J_file=None, factor_ah=None, use_infinite=False,
                       print_H=False, calc_dynmap=False, rho0=None, get_M_t=None, trajectories=None, n_sub=1,
-                      device=None, pulse_sampling="ace_file", trapz=None, dressed_rho=None):
+                      device=None, pulse_sampling="ace_file", trapz=None, dressed_rho=None, lower_only=False):
     """Propagate one trajectory (or a batch: `trajectories`) and return ACE's output table.
 
     Returns (1 + len(output_ops), n_t) complex, row 0 = time (general_system.py:104-110, 343).
@@ -262,6 +266,11 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
     (general_dressed_states.py:64-70); one table per trajectory with `trajectories`, all from one launch
     (pqd_dressed_states; semantic choices in DESIGN.md §2). dressed_rho (one (n_t, N, N) array per trajectory) makes
     every entry a (table, occupations (n_t, N)) pair, the occupations evaluated in the same launch.
+
+    lower_only=True returns the lowered problem instead of running it: Lowered(systems, traj_sys, grid, n_t), the
+    Systems (one per distinct drive and generator), each trajectory's system index, the output grid and each
+    trajectory's output count. No device is touched and no PT is resolved; the dim > 6 refusals hold as without it.
+    The dressed-state functions take H(t) of the cavity and sensor models from it (general_dressed_states.py).
     """
     if pulse_sampling not in ("exact", "ace_file"):
         raise ValueError(f"pulse_sampling must be 'exact' or 'ace_file', not {pulse_sampling!r}")
@@ -407,6 +416,10 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
             systems.append(make_system(pl, pfx, pfy, hamiltonian(sop), dissipators(lop)))
         traj_sys.append(sys_keys[key])
     system = systems[0]
+
+    if lower_only:
+        return Lowered(systems, traj_sys, grid,
+                       [(traj_steps[k] if trajectories is not None else n_steps) + 1 for k in range(len(traj_specs))])
 
     if dressedstates:
         # the table the reference reads from timedep_eigenstates' `.ds` file (:297-304): the eigenpairs of the param

@@ -15,7 +15,7 @@ from .. import constants
 hbar = constants.hbar
 temp_dir = constants.temp_dir
 
-_FWD = ("trajectories", "n_sub", "device", "pulse_sampling", "trapz", "dressed_rho")
+_FWD = ("trajectories", "n_sub", "device", "pulse_sampling", "trapz", "dressed_rho", "lower_only")
 
 
 def tls(t_start, t_end, *pulses, dt=0.1, gamma_e=1/100, phonons=False, t_mem=6.4, ae=5.0, temperature=4,
@@ -233,3 +233,16 @@ def tls_dressed_states(t_start, t_end, *pulses, plot=True, t_lim=None, e_lim=Non
     return dressed_states(tls, 2, t_start, t_end, *pulses, filename=filename, plot=plot, t_lim=t_lim, e_lim=e_lim,
                           firstonly=firstonly, colors=colors, visible_states=visible_states,
                           return_eigenvectors=return_eigenvectors, **options)
+
+
+def tls_photons_dressed_states(t_start, t_end, *pulses, plot=True, t_lim=None, e_lim=None,
+                               filename="tls_photons_dressed", firstonly=False, visible_states=None, print_states=None,
+                               **options):
+    """Dressed states of the two-level system in two cavity modes (pyaceqd/two_level_system/tls.py:207-212), dim
+    [2, n_phot1 + 1, n_phot2 + 1]: the reference's tuple, equally spaced colours. The reference needs n_phot1 and
+    n_phot2 among the options (KeyError otherwise); absent, tls_photons' defaults (2, 2: dim 18) are taken."""
+    from ..general_system.general_dressed_states import dressed_states
+    dim = [2, options.get("n_phot1", 2) + 1, options.get("n_phot2", 2) + 1]
+    return dressed_states(tls_photons, dim, t_start, t_end, *pulses, filename=filename, plot=plot, t_lim=t_lim,
+                          e_lim=e_lim, firstonly=firstonly, colors=None, visible_states=visible_states,
+                          print_states=print_states, **options)

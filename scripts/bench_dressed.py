@@ -1,4 +1,5 @@
-"""Throughput of the dressed-state launch (csrc/dressed.hip through engine.dressed_states) at the project's scan shapes.
+"""Throughput of the dressed-state launch (csrc/dressed.hip and csrc/dressed_wide.hip through engine.dressed_states) at
+the project's scan shapes.
 
 One problem per (scan point, output time): H(t) is built and diagonalised on the device, the occupations are evaluated
 against a density matrix per problem. Shapes (systems x output times):
@@ -6,6 +7,9 @@ against a density matrix per problem. Shapes (systems x output times):
   bx_large   biexciton, pulse-area scan                  2,048 x 10,001
   bx_small   biexciton                                     256 x 10,001
   six        six-level dot in an in-plane field             32 x 10,001
+  tlsph      tls_photons, dim 18 (dressed_wide.hip)        256 x  2,001
+  bxph       biexciton_photons, dim 16 (dressed_wide.hip)  256 x  2,001
+  sens24     tls_photon_two_sensor, dim 24 (")              32 x  2,001
 Each shape runs with and without the eigenvector download (eigenvalues and occupations always come back) and prints
 one JSON line per run:
   kernel_ms      median kernel duration from device events (pqd_dressed_timing), after a warm-up call, over enough
@@ -16,7 +20,9 @@ one JSON line per run:
                  is negligible
   eigh_*         numpy.linalg.eigh plus the occupation einsum on the same H(t) on the host (16 threads at most), on
                  `eigh_problems` of the problems (all of them up to --eigh-max); the only baseline there is
-usage: python scripts/bench_dressed.py [--shapes tls,bx_large,bx_small,six] [--eigh-max 400000] [--out FILE]
+At dim 18 the eigenvectors are 5 KB per problem (2.7 GB for tlsph): with them call_ms is the download.
+usage: python scripts/bench_dressed.py [--shapes tls,bx_large,bx_small,six,tlsph,bxph,sens24] [--eigh-max 400000]
+                                       [--out FILE]            (default shapes: the four of dim <= 6)
 """
 import argparse
 import json
@@ -31,7 +37,8 @@ sys.path.insert(0, HERE)
 
 HBM_PEAK = 8.0e12  # bytes / s
 
-SHAPES = {"tls": (2, 2048, 1001), "bx_large": (4, 2048, 10001), "bx_small": (4, 256, 10001), "six": (6, 32, 10001)}
+SHAPES = {"tls": (2, 2048, 1001), "bx_large": (4, 2048, 10001), "bx_small": (4, 256, 10001), "six": (6, 32, 10001),
+          "tlsph": (18, 256, 2001), "bxph": (16, 256, 2001), "sens24": (24, 32, 2001)}
 
 
 def build_systems(name, n_sys, n_t, dt):
@@ -39,10 +46,22 @@ def build_systems(name, n_sys, n_t, dt):
     from pyaceqd_amd import opgrammar
     from pyaceqd_amd.constants import hbar
     from pyaceqd_amd.engine import System
-    from pyaceqd_amd.four_level_system.linear import biexciton_ops
+    from pyaceqd_amd.four_level_system.linear import biexciton_ops, biexciton_photons_ops
     from pyaceqd_amd.six_level_system.linear import sixls_ops
+    from pyaceqd_amd.two_level_system.tls import tls_composite_ops
+    cav = (3, 0.06, 0.12 / hbar, -2)   # a cavity mode of the models' defaults: levels, coupling, loss, detuning
     if name == "tls":
         N, system_op, inter = 2, ["0.2*|1><1|_2"], [["|1><0|_2", "x"]]
+    elif name == "tlsph":
+        N = 18
+        system_op, _, _, inter = tls_composite_ops([cav, cav], [], 1 / 100, False, False, None, None)[:4]
+    elif name == "sens24":
+        N = 24
+        system_op, _, _, inter = tls_composite_ops([cav], [(0, 0.01), (0, 0.01)], 1 / 100, False, False, None,
+                                                   0.0001)[:4]
+    elif name == "bxph":
+        N = 16
+        system_op, _, _, inter, _ = biexciton_photons_ops(2, 2, delta_xy=0.1, delta_b=4)
     elif name.startswith("bx"):
         N = 4
         system_op, _, _, inter, _ = biexciton_ops(delta_xy=0.1, delta_b=4)
