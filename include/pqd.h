@@ -249,6 +249,10 @@ int pqd_plan_windows(const pqd_plan* plan, int32_t* on);
  * for the headline configuration only (N^2 = 16, chi = 64, 8 trajectories per workgroup, default switches; DESIGN.md
  * §4.1, PQD_SWEEP_LEAN=0 forces the general instance), else 0 */
 int pqd_plan_sweep_lean(const pqd_plan* plan, int32_t* on);
+/* 1 when the lean instance's launches of this plan read the outputs inside the fused column phase: some workgroup has
+ * steps after its last MTO and activation and before its last two steps (PQD_LEAN_RO=0 keeps the separate
+ * closure pass on every step), else 0. Results agree with the other readout to rounding (the order of two sums) */
+int pqd_plan_sweep_readout(const pqd_plan* plan, int32_t* on);
 /* every decision plan creation took, as one line of space-separated key=value pairs in a fixed order: the device's
  * CU count, path (PQD_PATH_*), workgroup shape, split / quad / multi-trajectory split / trunk layout, windows, the
  * A/B switches as the kernels will see them, and 64-bit FNV-1a hashes (hex) of the block arrays, the PT row-unit list

@@ -207,6 +207,10 @@ struct SweepParams {
     int colbig;              // N2 > 16 column phases: one pass over k for all of a wave's tiles (1, PQD_COLBIG; 0: per tile)
     int lean;                // 1: the plan has the headline configuration, the batched sweep runs its lean instance
                              //   (pt_sweep.hip LEAN; pqd_host.cpp sweep_lean_ok; PQD_SWEEP_LEAN=0: general instance)
+    const int* blk_fast;     // n_blocks, main blocks of a lean plan: first step from which every occupied slot enters
+                             //   each step fused, has no event left and is active (>= 1; INT_MAX: none before blk_end - 1):
+                             //   from there the outputs are read inside the column phase (pt_sweep.hip LeanCol).
+                             //   NULL: never (PQD_LEAN_RO=0, the trunk pre-pass, plans on the general instance)
 };
 
 // split groups with several trajectories per group (pt_msplit.hip)

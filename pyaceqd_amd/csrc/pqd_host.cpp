@@ -274,6 +274,8 @@ struct pqd_plan {
     DevBuf<FreePropSys> systab;
     FuseParams fu{};
     DevBuf<int> sched, blk_traj, blk_end, blk_sys, blk_act, blk_src, traj_sys, wbeg, wend, ev_start;
+    DevBuf<int> blk_fast;         // per block: first step of the lean instance's fast region (block_fast_steps)
+    bool lean_ro = false;         // some block of a lean plan has fast steps (pqd_plan_sweep_readout)
     int64_t traj_steps = 0;       // executed trajectory-steps per execute (shared trunks counted once)
     int branch = 1;               // shared-trunk activation in the batched sweep (PQD_BRANCH)
     // trunk pre-pass (pqd_host.cpp plan_trunks): one MTO-free trajectory per system writes the checkpoints the
@@ -471,7 +473,7 @@ void pqd_pt_destroy(pqd_pt* pt) { delete pt; }
 struct PlanEnv {
     int split, msplit, ms_tb, ms_ptm, fp4, fpm, pt_mode, cmul3, trpre, bt, colbig, trunk, quad, qpw, qcg, qprio, win,
         rowpair, ablate;
-    bool ms_l2, split_ow, split_gran, split_xcd, sweep_lean, pt_mode_set, fuse, branch, idle, unitbal, split_l2, hilbert;
+    bool ms_l2, split_ow, split_gran, split_xcd, sweep_lean, lean_ro, pt_mode_set, fuse, branch, idle, unitbal, split_l2, hilbert;
     unsigned split_spin;
 };
 
@@ -490,6 +492,7 @@ static PlanEnv read_plan_env() {
     v.fp4 = num("PQD_FP4", 1) != 0;             // N2 = 4 free propagators, 16 matrices per workgroup (0: general kernel)
     v.fpm = num("PQD_FPM", 1);                  // N2 = 25, 36 free propagators on the matrix cores (raw value; 0: LDS)
     v.sweep_lean = num("PQD_SWEEP_LEAN", 1) != 0;  // the lean sweep instance where the plan allows it (sweep_lean_ok)
+    v.lean_ro = num("PQD_LEAN_RO", 1) != 0;      // lean instance: outputs read inside the fused column phase (0: closure pass)
     v.pt_mode_set = set("PQD_PT_MODE");
     v.pt_mode = num("PQD_PT_MODE", 0);          // PT-row variant (raw value; unset: 5 at BT = 4, else 4)
     v.cmul3 = num("PQD_CMUL3", 1);              // 3M column products (raw value)
@@ -870,6 +873,7 @@ static void finalize_trunks(pqd_plan* P) {
     k.ev_start = P->tk_evstart.p; k.out = P->tk_out.p;
     k.ck_map = P->tk_ckmap.p; k.ck_stride = P->n_steps + 1;
     k.lean = 0;
+    k.blk_fast = nullptr;
     const int nw = P->tk_BT * sweep_wpt(P->N2, P->tk_BT, P->CHI);
     k.units = (P->sp.units ? P->tk_units.p : nullptr);
     k.umax = (int)(P->tk_units.n / nw);
@@ -1342,6 +1346,29 @@ static int upload_blocks(pqd_plan* P, Blocks& B, const pqd_traj* tr, const std::
     return PQD_OK;
 }
 
+// Per block, the first step of the lean instance's fast region (pt_sweep.hip LeanCol): from it on every occupied slot
+// enters each step fused, has no MTO event at that step or later, and was activated at an earlier step. A slot enters
+// step n fused when it was active at n - 1 and has no event at n (events are sorted by step per trajectory), so the step
+// is 1 + the largest activation or event step of the block's slots; INT_MAX where that leaves no fast step (the region
+// ends before the block's last PT step, n_end - 1: every fast step loads PT operands for its successor) or the block is
+// empty
+static std::vector<int> block_fast_steps(int BT, const Blocks& B, const MtoEvents& E) {
+    std::vector<int> bf(B.be.size(), INT_MAX);
+    for (size_t b = 0; b < B.be.size(); ++b) {
+        int64_t f = 1;
+        bool any = false;
+        for (int q = 0; q < BT; ++q) {
+            const int t = B.bt[b * BT + q];
+            if (t < 0) continue;
+            any = true;
+            f = std::max<int64_t>(f, (int64_t)B.ba[b * BT + q] + 1);
+            if (E.ev_start[t + 1] > E.ev_start[t]) f = std::max<int64_t>(f, (int64_t)E.evs[E.ev_start[t + 1] - 1].x + 1);
+        }
+        if (any && f < (int64_t)B.be[b] - 1) bf[b] = (int)f;
+    }
+    return bf;
+}
+
 // the free-propagator build of a plan: idle operators and pulse windows. After the trunks: windows need n_trunk == 0
 static int setup_free_props(pqd_plan* P, const pqd_grid* grid, const PlanEnv& env, hipStream_t s) {
     const int n_sys = P->n_sys, ns = P->n_steps;
@@ -1382,7 +1409,8 @@ static int setup_free_props(pqd_plan* P, const pqd_grid* grid, const PlanEnv& en
 
 // the launch parameters of the main sweep: the plan's buffers, the kernel variants, the PT row units, the fused
 // half steps, and whether the plan runs the lean instance
-static int fill_sweep_params(pqd_plan* P, const pqd_pt* pt, const PlanEnv& env, hipStream_t s) {
+static int fill_sweep_params(pqd_plan* P, const pqd_pt* pt, const PlanEnv& env, const std::vector<int>& blk_fast,
+                             hipStream_t s) {
     const int n_sys = P->n_sys, ns = P->n_steps, N2 = P->N2, n_out = P->n_out;
     const size_t m2 = (size_t)N2 * N2;
     SweepParams& sp = P->sp;
@@ -1449,6 +1477,13 @@ static int fill_sweep_params(pqd_plan* P, const pqd_pt* pt, const PlanEnv& env, 
     // a static bias between the grid halves gains nothing; profiles/r03/quad_prio.log)
     sp.qprio = env.qprio;
     sp.lean = sweep_lean_ok(P, sp, env) ? 1 : 0;
+    // the lean instance's readout inside the fused column phase (PQD_LEAN_RO=0: the closure pass on every step). The
+    // table is the plan's last allocation, so the buffers before it lie where they did
+    if (sp.lean && env.lean_ro) {
+        HIPCHK(P->blk_fast.upload(blk_fast.data(), blk_fast.size(), s));
+        sp.blk_fast = P->blk_fast.p;
+        for (int f : blk_fast) P->lean_ro = P->lean_ro || f != INT_MAX;
+    }
     return PQD_OK;
 }
 
@@ -1702,10 +1737,11 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
     TrunkChoice tc = choose_trunks(sh, pc, B, to, tsys, tr, branch_on && fuse_on, env.trunk, caps.n_cu);
     if (tc.use_trunk && (rc = apply_trunks(P, tc, B, tsys, pt, env, caps, s))) return rc;
     if ((rc = upload_blocks(P, B, tr, sch, s))) return rc;
+    const std::vector<int> blk_fast = block_fast_steps(pc.BT, B, E);
 
     // launch parameters
     if ((rc = setup_free_props(P, grid, env, s))) return rc;
-    if ((rc = fill_sweep_params(P, pt, env, s))) return rc;
+    if ((rc = fill_sweep_params(P, pt, env, blk_fast, s))) return rc;
     finalize_trunks(P);
     if (pc.split) {
         HIPCHK(P->Xs.alloc((size_t)n_traj * 4 * N2 * P->CHI));  // split exchange: 2 slots of granules
@@ -1926,6 +1962,12 @@ int pqd_plan_windows(const pqd_plan* P, int32_t* on) {
 int pqd_plan_sweep_lean(const pqd_plan* P, int32_t* on) {
     if (!P || !on) return fail(PQD_ERR_ARG, "NULL argument");
     *on = (P->sp.lean && !P->nopt && !P->split && !P->msplit && !P->quad) ? 1 : 0;
+    return PQD_OK;
+}
+
+int pqd_plan_sweep_readout(const pqd_plan* P, int32_t* on) {
+    if (!P || !on) return fail(PQD_ERR_ARG, "NULL argument");
+    *on = (P->sp.lean && P->lean_ro && !P->nopt && !P->split && !P->msplit && !P->quad) ? 1 : 0;
     return PQD_OK;
 }
 

@@ -493,14 +493,15 @@ struct LeanPt {
                 for (int g = 0; g < NG; ++g)
                     wr[r][rb][16 * g] = dbl2{p1[r][rb][g] - p2[r][rb][g], p3[r][rb][g] - p1[r][rb][g] - p2[r][rb][g]};
     }
-    // unit e = (slice, row 0, row 1 or -1, -) of one or two rows; en: the wave's next unit (MORE). The first row's
+    // unit e = (slice, row 0, row 1 or -1, -) of one or two rows; en: the wave's next unit (MORE), a slice of the set Qns
+    // (this step's, or the next step's for the first unit of that step). The first row's
     // addresses and its k-step 0 are common to both sizes and issued ahead of the branch (and of the first wait for
     // the slice, which the compiler places there)
     template <bool MORE>
     static __device__ __forceinline__ void unit_r(dbl2 (&qn)[PF][NG], const double2* Qs, int4 e, int4 en, unsigned qoff,
-                                                  const double2* xl, double2* wl) {
+                                                  const double2* xl, double2* wl, const double2* Qns) {
         const double2* Qu = Qs + (size_t)e.x * CHI * CHI;
-        const double2* Qnext = Qs + (size_t)(MORE ? en.x : e.x) * CHI * CHI;
+        const double2* Qnext = Qns + (size_t)(MORE ? en.x : e.x) * CHI * CHI;
         const LdsC2* x0[RB];
         LdsC2* w0[RB];
         dbl2 a0[RB];
@@ -532,6 +533,22 @@ struct LeanPt {
         }
     }
 
+    // run() with the slice pipeline kept full across steps (the fast region of the step loop): qn holds k-steps
+    // 0 .. PF - 1 of u0's slice of this step's set Qs on entry and those of u0's slice of the next step's set Qn on return:
+    // the wave's last unit loads them in its last PF k-steps, so no L2 round trip is exposed behind the barrier that opens
+    // the next PT phase, and every unit body is "in flight at entry, loads a successor at exit". Bounds: k-steps
+    // 0 .. PF - 1 of a slice the unit list names, in the set the schedule names for the next step; the caller runs this
+    // only where that step is itself a PT step of the block (never in the block's last one)
+    static __device__ __forceinline__ void run_pre(dbl2 (&qn)[PF][NG], const double2* Qs, const double2* Qn, int4 u0,
+                                                   int4 u1, unsigned qoff, const double2* xl, double2* wl) {
+        if (u0.x < 0) return;
+        int4 e = u0;
+        if (u1.x >= 0) {
+            unit_r<true>(qn, Qs, u0, u1, qoff, xl, wl, Qs);
+            e = u1;
+        }
+        unit_r<true>(qn, Qs, e, u0, qoff, xl, wl, Qn);
+    }
     // the wave's units u0 and u1 (slice, row 0, row 1 or -1, -; slice < 0: none) on the step's slice set Qs
     static __device__ __forceinline__ void run(const double2* Qs, int4 u0, int4 u1, unsigned qoff, const double2* xl,
                                                double2* wl) {
@@ -540,10 +557,146 @@ struct LeanPt {
         ldq_first(qn, Qs + (size_t)u0.x * CHI * CHI, qoff);
         int4 e = u0;
         if (u1.x >= 0) {
-            unit_r<true>(qn, Qs, u0, u1, qoff, xl, wl);
+            unit_r<true>(qn, Qs, u0, u1, qoff, xl, wl, Qs);
             e = u1;
         }
-        unit_r<false>(qn, Qs, e, e, qoff, xl, wl);
+        unit_r<false>(qn, Qs, e, e, qoff, xl, wl, Qs);
+    }
+};
+
+// Two sums over lane pairs W = 16 or 32 apart in one step of a reduce-scatter: v_permlane16_swap exchanges the odd 16-lane
+// rows of its first operand with the even rows of its second (v_permlane32_swap: the upper 32 lanes with the lower 32),
+// so the sum of its two results is a[l] + a[l ^ W] in the lanes with bit W clear and b[l] + b[l ^ W] in the others
+template <int W>
+__device__ __forceinline__ double lean_pair(double a, double b) {
+    static_assert(W == 32 || W == 16, "permlane swaps pair lanes 32 or 16 apart");
+    const long long A = __double_as_longlong(a), B = __double_as_longlong(b);
+    unsigned l0, l1, h0, h1;
+    if constexpr (W == 32) {
+        const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)A, (unsigned)B, false, false);
+        const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(A >> 32), (unsigned)(B >> 32), false, false);
+        l0 = lo[0]; l1 = lo[1]; h0 = hi[0]; h1 = hi[1];
+    } else {
+        const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)A, (unsigned)B, false, false);
+        const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(A >> 32), (unsigned)(B >> 32), false, false);
+        l0 = lo[0]; l1 = lo[1]; h0 = hi[0]; h1 = hi[1];
+    }
+    return __longlong_as_double(((long long)h0 << 32) | l0) + __longlong_as_double(((long long)h1 << 32) | l1);
+}
+// v[q] summed over the wave's four 16-lane rows (lanes l, l ^ 16, l ^ 32, l ^ 48), left in the lanes of row q
+__device__ __forceinline__ double lean_rows4(const double (&v)[4]) {
+    return lean_pair<32>(lean_pair<16>(v[0], v[1]), lean_pair<16>(v[2], v[3]));
+}
+
+// sum over each 16-lane row, left in all its lanes (c_group_sum<16> with bound_ctrl DPP moves: every lane of these
+// permutations has a source, so no destination is initialised first)
+template <int CTRL>
+__device__ __forceinline__ double lean_dpp(double v) {
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, true);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+__device__ __forceinline__ double2 lean_row_sum(double2 v) {
+    v = c_add(v, make_double2(lean_dpp<0xB1>(v.x), lean_dpp<0xB1>(v.y)));    // quad_perm [1,0,3,2]
+    v = c_add(v, make_double2(lean_dpp<0x4E>(v.x), lean_dpp<0x4E>(v.y)));    // quad_perm [2,3,0,1]
+    v = c_add(v, make_double2(lean_dpp<0x141>(v.x), lean_dpp<0x141>(v.y)));  // row_half_mirror
+    return c_add(v, make_double2(lean_dpp<0x140>(v.x), lean_dpp<0x140>(v.y)));  // row_mirror
+}
+
+// The fused column operator F(n) of the lean instance with the step's outputs read on the way (N2 = 16, chi = 64, one
+// wave per trajectory). The state the outputs of a fused step are read from is the one before F(n), and the wave that
+// applies F(n) loads exactly those values as its B operands: lane (li, lk) = (lane & 15, lane >> 4) holds
+// S[4 ks + lk][16 nt + li] for all 4 x 4 (ks, nt). So the closure r[a] = sum_d S[a][d] c[d] is one complex MAC per loaded
+// value into r[ks] (the lane's part of rows 4 ks + lk), the trace t[k] = sum_a W(n)[k][a] r[a] 4 n_out MACs, and the sum
+// over the 64 lanes a reduce-scatter of permlane swaps and a DPP row sum: no second pass over the states, no partials in
+// LDS, no other wave involved. The MFMAs are those of col_apply_mfma3 with the same operands in the same order per
+// accumulator and the same combine, so the states are bit-identical to it; the outputs differ from the closure pass of
+// the step loop by the order of a 64-term and a 16-term sum.
+// State addresses: one per-lane LDS base (row lk, column li of the wave's trajectory), every read S[4 ks + lk][16 nt + li]
+// and every write S[lk + 4 r][16 nt + li] at base + (4 j RS + 16 nt) 16 B, j < 4: the DS immediate (largest 12 RS 16 + 768).
+// Bounds: F, W and the closure vector are indexed as the step loop's own loads of them (row li < 16 and column
+// 4 ks + lk < 16 of F(n), n < n_steps; W(n)[k][4 ks + lk], k < n_out; c[16 nt + li] < CHI of slice set sched[n - 1]).
+template <int RS, bool READOUT>
+struct LeanCol {
+    static constexpr int N2 = 16, CHI = 64, KS = 4, NTL = 4, KMAX = 4;   // KMAX: the lean instance's limit on n_out
+    typedef double dbl2 __attribute__((ext_vector_type(2)));
+    typedef __attribute__((address_space(3))) dbl2 LdsC2;
+    static_assert((12 * RS + 48) * 16 + 15 < 65536, "tile and row offsets fit the DS immediate");
+
+    // Fn: F(n) of the wave's system; cv: closure vector of the slice set of step n - 1; Wn: W(n) of the wave's system;
+    // sb: the lane's LDS base; out: where the slot's n_out outputs of step n go (READOUT only)
+    static __device__ __forceinline__ void run(const double2* __restrict__ Fn, const double2* __restrict__ cv,
+                                               const double2* __restrict__ Wn, int n_out, LdsC2* sb, double2* out,
+                                               int lane) {
+        const int li = lane & 15, lk = lane >> 4;
+        double2 ac[KS], cl[NTL], w[KMAX][KS];
+        double as[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) ac[ks] = Fn[li * N2 + 4 * ks + lk];
+        if constexpr (READOUT) {
+#pragma unroll
+            for (int nt = 0; nt < NTL; ++nt) cl[nt] = cv[16 * nt + li];
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k)
+                if (k < n_out) {
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) w[k][ks] = Wn[k * N2 + 4 * ks + lk];
+                }
+        }
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) as[ks] = ac[ks].x + ac[ks].y;
+        double2 r[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) r[ks] = c_zero();
+        // a tile's four operand values are read while the tile before it runs its MFMAs (one LDS round trip exposed per
+        // step, not one per value; tiles are disjoint columns, so the in-place writes of a tile touch nothing read later)
+        dbl2 bn[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) bn[ks] = sb[4 * ks * RS];
+#pragma unroll
+        for (int nt = 0; nt < NTL; ++nt) {
+            dbl4 p1 = dbl4{0, 0, 0, 0}, p2 = p1, p3 = p1;
+            dbl2 bq[KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                bq[ks] = bn[ks];
+                if (nt + 1 < NTL) bn[ks] = sb[4 * ks * RS + 16 * (nt + 1)];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const dbl2 bv = bq[ks];
+                const double bs = bv.x + bv.y;
+                p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[ks].x, bv.x, p1, 0, 0, 0);
+                p2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[ks].y, bv.y, p2, 0, 0, 0);
+                p3 = __builtin_amdgcn_mfma_f64_16x16x4f64(as[ks], bs, p3, 0, 0, 0);
+                if constexpr (READOUT) c_fma(r[ks], make_double2(bv.x, bv.y), cl[nt]);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sb[4 * j * RS + 16 * nt] = dbl2{p1[j] - p2[j], p3[j] - p1[j] - p2[j]};
+        }
+        if constexpr (READOUT) {
+            // t[k] over the lane's rows; re[k], im[k] = 0 for k >= n_out
+            double re[KMAX], im[KMAX];
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k) {
+                double2 t = c_zero();
+                if (k < n_out) {
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) c_fma(t, w[k][ks], r[ks]);
+                }
+                re[k] = t.x;
+                im[k] = t.y;
+            }
+            // the four 16-lane rows: after the swaps row q holds output q's sum over the rows (lean_rows4), then the
+            // sum over the row's 16 lanes; lane 16 q stores output q
+            double2 y = make_double2(lean_rows4(re), lean_rows4(im));
+            y = lean_row_sum(y);
+            if (li == 0 && lk < n_out) out[lk] = y;
+        }
+        // the PT phase reads what other lanes and waves wrote: the barrier that follows waits for these writes
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
 };
 
@@ -602,7 +755,8 @@ __device__ __forceinline__ void pt_row_mfma16(const double2* __restrict__ Qg, do
 // stay in scalar registers (200.3 -> 196.1 ms per bench launch; the instance alone gains nothing, and
 // a register for the next event step or the first slice k-step loaded before the PT barrier measured slower).
 // Its PT phase is LeanPt above (184.2 against 193.8 ms; the fused column operator loaded a phase ahead and a static
-// s_setprio for waves 4-7 both measured slower on top of it and are not here).
+// s_setprio for waves 4-7 both measured slower on top of it and are not here). From a block's last MTO and activation on
+// it reads the outputs inside the fused column operator (LeanCol above; the fast region of the step loop: 184.7 -> 178.9 ms).
 // slice k-steps in flight in the lean instance's PT phase (2 measured the same within the spread and takes all 256 VGPRs)
 constexpr int LEAN_PF = 1;
 template <int N2, int CHI, int BT, bool TRUNK, bool LEAN = false>
@@ -723,7 +877,69 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
     const unsigned lean_qoff = (unsigned)((pq * CHI + pj) * sizeof(double2));
     const double2* lean_xl = st + pq + (lane & 3) * TS;
     double2* lean_wl = st + pj + pq * TS;
+    // lean: the fast region of the block (SweepParams::blk_fast) and, wave-uniform, the output window of this wave's slot
+    // and its system's W rows, read once through the scalar cache
+    int blk_fast = INT_MAX, w_beg = INT_MAX, w_end = -1;
+    long long w_off = 0;
+    const double2* Ww = Wg;
+    if constexpr (LEAN) {
+        if (p.blk_fast) blk_fast = ldc(p.blk_fast + blockIdx.x);
+        const int t = __builtin_amdgcn_readfirstlane(s_traj[tw]);
+        if (t >= 0) {
+            w_beg = ldc(p.wbeg + t);
+            w_end = ldc(p.wend + t);
+            const int* wo = (const int*)(p.woff + t);
+            w_off = (long long)(((unsigned long long)(unsigned)ldc(wo + 1) << 32) | (unsigned)ldc(wo));
+            Ww += (size_t)ldc(p.traj_sys + t) * p.w_stride;
+        }
+    }
     for (int n = n0;; ++n) {
+        // ------------------------------------------------------------ lean: the fast region, blk_fast <= n < n_end - 1
+        // Every occupied slot is active, enters each of these steps fused and has no event left, so a step is the column
+        // operator F(n) with the outputs read from its operands (LeanCol), a barrier, the PT phase and a barrier: no
+        // closure pass, no partials in LDS, no fused flags written (they stay 1, as the last step before the region left
+        // them) and no barrier at the end of the step (the column operator touches the wave's own trajectory only).
+        // Every PT phase here loads the first slice k-step of the next one (LeanPt::run_pre), so the region ends a step
+        // before the block's last PT step: steps n_end - 1 and n_end (outputs only) run below as before, the first of them
+        // with its W row elements fetched here, and nothing is loaded for a step the block does not run.
+        if constexpr (LEAN) {
+            if (n >= blk_fast && n < n_end - 1) {
+                using LC = LeanCol<RS, true>;
+                typename LC::LdsC2* sb;
+                {
+                    unsigned v = (unsigned)(size_t)((typename LC::LdsC2*)stw + pq * RS + pj);
+                    asm("" : "+v"(v));
+                    sb = (typename LC::LdsC2*)v;
+                }
+                const bool occupied = my_act != INT_MAX;
+                // the first k-step of the wave's first unit, in flight from one step's PT phase to the next's
+                using LP = LeanPt<CHI, RS, TS, LEAN_PF>;
+                typename LP::dbl2 qn[LEAN_PF][CHI / 16];
+                if (u0.x >= 0) LP::ldq_first(qn, Qg0 + ((size_t)sc_cur * p.D + u0.x) * CHI * CHI, lean_qoff);
+                for (; n < n_end - 1; ++n) {
+                    sc_nxt = ldc(p.sched + (n + 1 < p.n_steps ? n + 1 : p.n_steps - 1));
+                    if (occupied) {
+                        const double2* Fn = Fg + (size_t)n * N2 * N2;
+                        if (w_beg <= n && n <= w_end)   // the store's predicate: the slot's window, wave-uniform
+                            LC::run(Fn, p.closure + (size_t)sc_prev * CHI, Ww + (size_t)n * p.n_out * N2, p.n_out, sb,
+                                    outg + w_off + (long long)(n - w_beg) * p.n_out, lane);
+                        else
+                            LeanCol<RS, false>::run(Fn, nullptr, nullptr, 0, sb, nullptr, lane);
+                    }
+                    __syncthreads();
+                    LP::run_pre(qn, Qg0 + (size_t)sc_cur * p.D * CHI * CHI, Qg0 + (size_t)sc_nxt * p.D * CHI * CHI, u0, u1,
+                                lean_qoff, lean_xl, lean_wl);
+                    __syncthreads();
+                    sc_prev = sc_cur;
+                    sc_cur = sc_nxt;
+                }
+                fz = true;
+                if (tid < ntr) {  // W(n_end - 1) row element for the traces below
+                    const int a = tid % N2, bk = tid / N2, b = bk / p.n_out, k = bk - (bk / p.n_out) * p.n_out;
+                    wpre = Wg[(size_t)s_sys[b] * p.w_stride + ((size_t)n * p.n_out + k) * N2 + a];
+                }
+            }
+        }
         // ------------------------------------------------------------ shared-trunk activations at step n
         if (n == next_act) {
             // a checkpoint (src <= -2) holds the trunk at the top of step n >= 1 with M_b(n-1) deferred (fused)

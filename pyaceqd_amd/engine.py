@@ -455,6 +455,13 @@ class Plan:
         _lib.check(_lib.lib().pqd_plan_sweep_lean(self.handle, C.byref(on)))
         return bool(on.value)
 
+    def sweep_readout(self):
+        """True when the lean instance reads this plan's outputs inside its fused column phase: some workgroup has steps
+        after its last MTO and before its last two steps (PQD_LEAN_RO=0 keeps the closure pass everywhere)"""
+        on = C.c_int32()
+        _lib.check(_lib.lib().pqd_plan_sweep_readout(self.handle, C.byref(on)))
+        return bool(on.value)
+
     def describe(self):
         """every decision plan creation took (pqd_plan_describe) as a dict of strings: path, workgroup shape, split /
         quad / trunk layout, windows, the A/B switches, and hashes of the block, row-unit and group tables"""
