@@ -117,6 +117,11 @@ void pqd_ctx_destroy(pqd_ctx* ctx);
 int pqd_ctx_synchronize(pqd_ctx* ctx);
 
 int pqd_pt_create(pqd_ctx* ctx, int32_t dim, const pqd_pt_desc* desc, pqd_pt** out);
+/* The same PT for the Hilbert-space path with a PT (PQD_PATH_HILBERT_PT): dim in [2, 24] (PQD_ERR_UNSUPPORTED "dim %d
+ * not in [2, 24]" otherwise), chi in [1, 256], pqd_pt_create's argument checks, all before any device call. The slices
+ * are stored as given (no bond padding). A plan or propagate call handed such a handle runs that path at any dim,
+ * dim <= 6 included; pqd_pt_create's handles choose as before. Destroyed with pqd_pt_destroy. */
+int pqd_pt_create_wide(pqd_ctx* ctx, int32_t dim, const pqd_pt_desc* desc, pqd_pt** out);
 void pqd_pt_destroy(pqd_pt* pt);
 
 /* Reading the PT files ACE writes with `write_PT <name>`: <name>_initial, <name>_initial_0, <name>_repeated,
@@ -165,10 +170,12 @@ int pqd_dressed_timing(pqd_ctx* ctx, double* ms_kernel);
 
 /* one-shot: upload, propagate, download. pt may be NULL (no phonons); sched[n_steps] selects the
  * PT slice per step (NULL: min(n, n_slices-1)). rho0: N*N. out_ops: n_out*N*N.
- * Limits (PQD_ERR_UNSUPPORTED beyond them), for this call and every propagate / plan call below: with a PT dim in
- * [2, 6]; without one dim in [2, 24], where dim > 6 takes at most 8 jump operators and a Liouvillian whose norm bound
- * times a sub-step stays below 4096 (PQD_PATH_HILBERT); n_chan <= 4. pqd_pt_create, pqd_free_propagators,
- * pqd_dressed_states and the map-chain calls keep dim <= 6. */
+ * Limits (PQD_ERR_UNSUPPORTED beyond them), for this call and every propagate / plan call below: with a PT of
+ * pqd_pt_create dim in [2, 6]; without one dim in [2, 24], where dim > 6 takes at most 8 jump operators and a
+ * Liouvillian whose norm bound times a sub-step stays below 4096 (PQD_PATH_HILBERT); with a PT of pqd_pt_create_wide
+ * dim in [2, 24] equal to the PT's, at most 8 jump operators and the same norm bound at every dim, chi <= 256
+ * (PQD_PATH_HILBERT_PT; its workspace of n_traj chi dim^2 16 bytes: PQD_ERR_NOMEM when it cannot be allocated);
+ * n_chan <= 4. pqd_pt_create, pqd_free_propagators, pqd_dressed_states and the map-chain calls keep dim <= 6. */
 int pqd_propagate(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* grid, const pqd_pt* pt,
                   const int32_t* sched, const pqd_c128* rho0, int32_t n_out, const pqd_c128* out_ops,
                   const pqd_traj* traj, pqd_c128* out, int64_t out_len);
@@ -238,6 +245,9 @@ int pqd_plan_trapz(pqd_plan* plan, int32_t n_pairs, const int32_t* k_head, const
 #define PQD_PATH_HILBERT 5  /* no PT, dim 7..24 (dim <= 6 under PQD_HILBERT=1): one workgroup per trajectory, rho as an
                                N x N matrix, exp(L w) applied matrix-free (lind_hilbert.hip). bt is 1, there are no free
                                propagators (rebuild_free is ignored, ms_free is 0, no windows, no lean instance) */
+#define PQD_PATH_HILBERT_PT 6  /* a PT of pqd_pt_create_wide, dim 2..24: one workgroup per trajectory, rho (x) bond as chi
+                               N x N slices in a workspace, the half steps of PQD_PATH_HILBERT on every slice, the PT
+                               slice per element (lind_hilbert_pt.hip). bt, free propagators, windows, lean: as path 5 */
 /* the path the plan runs now, its trajectories per workgroup, how many split launches fell back, and the
  * trajectory-steps one execute propagates (trajectories of one system that share a lock-step workgroup propagate
  * their common MTO-free trunk once: PQD_BRANCH) */

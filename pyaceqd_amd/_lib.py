@@ -20,6 +20,7 @@ class PQDError(RuntimeError):
 PQD_ERR_UNSUPPORTED = 3
 PQD_PATH_NOPT = 0
 PQD_PATH_HILBERT = 5  # no PT, dim 7..24 (dim <= 6 under PQD_HILBERT=1): the Hilbert-space kernel (include/pqd.h)
+PQD_PATH_HILBERT_PT = 6  # a wide PT handle (pqd_pt_create_wide), dim 2..24: the Hilbert-space kernel with a PT
 HILBERT_MAX_DIM = 24  # largest dim of a plan without PT; everything that builds N^2 x N^2 superoperators stops at 6
 
 
@@ -74,6 +75,7 @@ _SIGS = {
     "pqd_ctx_destroy": ([C.c_void_p], None),
     "pqd_ctx_synchronize": ([C.c_void_p], C.c_int),
     "pqd_pt_create": ([C.c_void_p, C.c_int32, C.POINTER(pqd_pt_desc), C.POINTER(C.c_void_p)], C.c_int),
+    "pqd_pt_create_wide": ([C.c_void_p, C.c_int32, C.POINTER(pqd_pt_desc), C.POINTER(C.c_void_p)], C.c_int),
     "pqd_pt_destroy": ([C.c_void_p], None),
     "pqd_ace_pt_shape": ([C.c_char_p, C.c_int32, C.POINTER(pqd_ace_pt_dims)], C.c_int),
     "pqd_ace_pt_read": ([C.c_char_p, C.c_int32, C.POINTER(pqd_ace_pt_dims), P_C128, P_C128, P_C128, P_C128, P_I32],

@@ -354,6 +354,31 @@ struct HilbertParams {
 size_t hilbert_csr_bytes(int N, int n_lind, int nnz);  // LDS bytes of one system's nonzero lists (a multiple of 16)
 hipError_t launch_hilbert(int n_traj, const HilbertParams& p, hipStream_t s);
 
+// Hilbert-space propagation with a process tensor (lind_hilbert_pt.hip): the state rho (x) bond as chi slices of N x N
+// in a per-plan workspace, the free half steps of lind_hilbert.hip on G slices at a time, the PT slice per element
+constexpr int HBPT_EB = 8;         // elements of one dictionary entry contracted together (one PT unit)
+constexpr int HBPT_NT_MAX = 768;   // threads of the largest workgroup (12 waves: 3 per SIMD, 168 VGPRs as at 576)
+constexpr int HBPT_LDS_MAX = 160 * 1024;
+struct HilbertPtParams {
+    HilbertParams h;         // systems, grid, outputs, MTOs: exactly the no-PT path's (h.rho0 is rho0 without the bond)
+    int chi, D, G;           // bond dimension (slices are not padded), dictionary entries, slices in flight
+    const double2* Q;        // [n_slices][D][chi][chi]
+    const double2* closure;  // [n_slices][chi]
+    const double2* closure0; // chi
+    const double2* bond0;    // chi
+    const int* sched;        // slice of every step
+    double2* X;              // workspace [n_traj][chi][N*N]
+    // PT units: up to HBPT_EB elements that share one dictionary entry, ordered by entry (host-built permutation)
+    const int* unit_g;       // n_units
+    const int* unit_el;      // n_units * HBPT_EB element indices, -1: none
+    int n_units, ut;         // ut: units per LDS tile
+    int lds_elems;           // LDS work area in 16-byte elements (the matrices, or a PT tile if that is larger)
+};
+// LDS work area (16-byte elements) of G slices in flight, and what one PT unit takes
+constexpr size_t hbpt_mat_elems(int N, int nl_max, int G) { return (size_t)(2 + G * (3 + nl_max)) * N * N; }
+constexpr size_t hbpt_unit_elems(int chi) { return (size_t)HBPT_EB * (chi | 1); }
+hipError_t launch_hilbert_pt(int n_traj, const HilbertPtParams& p, hipStream_t s);
+
 // launchers (defined in the .hip translation units)
 hipError_t launch_dressed(int N, const DressedParams& p, hipStream_t s);       // N = 2..6 (dressed.hip)
 hipError_t launch_dressed_wide(int N, const DressedParams& p, hipStream_t s);  // N = 7..24 (dressed_wide.hip)

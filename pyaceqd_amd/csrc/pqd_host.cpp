@@ -246,6 +246,7 @@ struct pqd_pt {
     DevBuf<double> Qsum;      // Re + Im of every slice element (the 3M operand of the TLS quad kernel; N2 = 4 only)
     DevBuf<int> gmap;
     std::vector<int> gmap_h;  // host copy: the plan derives its PT row units from it
+    bool wide = false;        // pqd_pt_create_wide: slices as given (CHI = chi), for lind_hilbert_pt.hip only
 };
 
 struct pqd_plan {
@@ -298,6 +299,11 @@ struct pqd_plan {
     // plan's M, F, W, blocks, trunks and superoperators stay empty
     bool hilbert = false;
     HilbertParams hp{};
+    // the same with a wide PT (lind_hilbert_pt.hip): hp plus the bond workspace and the PT units
+    bool hilbert_pt = false;
+    HilbertPtParams hq{};
+    DevBuf<double2> hq_X;
+    DevBuf<int> hq_unit_g, hq_unit_el;
     DevBuf<HilbertSys> hb_systab;
     DevBuf<double2> hb_K0, hb_Xs, hb_Xt, hb_val, hb_valg;
     DevBuf<int> hb_row, hb_col;
@@ -461,6 +467,34 @@ int pqd_pt_create(pqd_ctx* ctx, int32_t dim, const pqd_pt_desc* d, pqd_pt** out)
     return PQD_OK;
 }
 
+int pqd_pt_create_wide(pqd_ctx* ctx, int32_t dim, const pqd_pt_desc* d, pqd_pt** out) {
+    if (!ctx || !d || !out) return fail(PQD_ERR_ARG, "NULL argument");
+    if (dim < 2 || dim > HB_NMAX) return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [2, %d]", dim, HB_NMAX);
+    const int N2 = dim * dim;
+    if (d->chi < 1 || d->chi > 256) return fail(PQD_ERR_UNSUPPORTED, "chi %d not in [1, 256]", d->chi);
+    if (d->D < 1 || d->n_slices < 1) return fail(PQD_ERR_ARG, "D and n_slices must be >= 1");
+    if (!d->Q || !d->closure || !d->closure0 || !d->bond0 || !d->gmap) return fail(PQD_ERR_ARG, "NULL PT array");
+    for (int a = 0; a < N2; ++a)
+        if (d->gmap[a] < 0 || d->gmap[a] >= d->D) return fail(PQD_ERR_ARG, "gmap[%d]=%d out of [0,%d)", a, d->gmap[a], d->D);
+    HIPCHK(hipSetDevice(ctx->device));
+    const int chi = d->chi;
+    auto pt = std::make_unique<pqd_pt>();
+    pt->ctx = ctx; pt->dim = dim; pt->chi = chi; pt->CHI = chi; pt->D = d->D; pt->n_slices = d->n_slices;
+    pt->wide = true;
+    pt->gmap_h.assign(d->gmap, d->gmap + N2);
+    hipStream_t s = ctx->stream;
+    hipError_t e = pt->Q.upload(reinterpret_cast<const double2*>(d->Q), (size_t)d->n_slices * d->D * chi * chi, s);
+    if (e == hipSuccess) e = pt->closure.upload(reinterpret_cast<const double2*>(d->closure), (size_t)d->n_slices * chi, s);
+    if (e == hipSuccess) e = pt->closure0.upload(reinterpret_cast<const double2*>(d->closure0), chi, s);
+    if (e == hipSuccess) e = pt->bond0.upload(reinterpret_cast<const double2*>(d->bond0), chi, s);
+    if (e == hipSuccess) e = pt->gmap.upload(d->gmap, N2, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the uploads read the caller's arrays
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? PQD_ERR_NOMEM : PQD_ERR_HIP, "PT upload: %s", hipGetErrorString(e));
+    *out = pt.release();
+    return PQD_OK;
+}
+
 void pqd_pt_destroy(pqd_pt* pt) { delete pt; }
 
 // Every PQD_* switch that plan creation and pqd_free_propagators read (A/B only: the defaults are the measured-best
@@ -472,7 +506,7 @@ void pqd_pt_destroy(pqd_pt* pt) { delete pt; }
 // each has one field.
 struct PlanEnv {
     int split, msplit, ms_tb, ms_ptm, fp4, fpm, pt_mode, cmul3, trpre, bt, colbig, trunk, quad, qpw, qcg, qprio, win,
-        rowpair, ablate;
+        rowpair, ablate, hbpt_g;
     bool ms_l2, split_ow, split_gran, split_xcd, sweep_lean, lean_ro, pt_mode_set, fuse, branch, idle, unitbal, split_l2, hilbert;
     unsigned split_spin;
 };
@@ -515,6 +549,7 @@ static PlanEnv read_plan_env() {
     v.split_spin = spin ? (unsigned)strtoul(spin, nullptr, 10) : (1u << 22);  // polls before a split wait times out (~0.1 s)
     v.split_l2 = num("PQD_SPLIT_L2", 1) != 0;   // split exchange lines kept in L2 (0: sc1 stores)
     v.hilbert = num("PQD_HILBERT", 0) == 1;     // 1: no-PT plans of dim <= 6 run the Hilbert-space kernel too (dim > 6 always)
+    v.hbpt_g = num("PQD_HBPT_G", 0);            // wide PT: at most this many bond slices in flight (raw value; <= 0: no cap)
     return v;
 }
 
@@ -903,11 +938,14 @@ static int check_plan_args(pqd_ctx* ctx, int32_t n_sys, const pqd_system* system
     if (n_sys > 1 && !traj_sys) return fail(PQD_ERR_ARG, "traj_sys is NULL with n_sys > 1");
     int rc = 0;
     for (int k = 0; k < n_sys; ++k) {
-        if ((rc = check_system(&systems[k], pt ? 6 : HB_NMAX))) return rc;
+        if ((rc = check_system(&systems[k], pt && !pt->wide ? 6 : HB_NMAX))) return rc;
         if (systems[k].dim != systems[0].dim) return fail(PQD_ERR_ARG, "system %d: dim %d != %d", k, systems[k].dim, systems[0].dim);
         if (systems[k].dim > 6 && systems[k].n_lind > HB_LMAX)  // dim > 6 runs in Hilbert space only (lind_hilbert.hip)
             return fail(PQD_ERR_UNSUPPORTED, "system %d: n_lind %d not in [0, %d] at dim %d > 6", k, systems[k].n_lind,
                         HB_LMAX, systems[k].dim);
+        if (pt && pt->wide && systems[k].n_lind > HB_LMAX)  // a wide PT runs in Hilbert space at every dim
+            return fail(PQD_ERR_UNSUPPORTED, "system %d: n_lind %d not in [0, %d] with a wide PT", k, systems[k].n_lind,
+                        HB_LMAX);
     }
     const pqd_system* sys = systems;
     for (int t = 0; t < tr->n_traj; ++t)
@@ -921,7 +959,7 @@ static int check_plan_args(pqd_ctx* ctx, int32_t n_sys, const pqd_system* system
     if (pt) {
         if (pt->ctx != ctx) return fail(PQD_ERR_ARG, "PT belongs to another context");
         if (pt->dim != N) return fail(PQD_ERR_ARG, "PT dim %d != system dim %d", pt->dim, N);
-        if (!sweep_supported(N2, pt->CHI) && !(pt->CHI == 256 && msplit_supported(N2, pt->CHI, n_out)))
+        if (!pt->wide && !sweep_supported(N2, pt->CHI) && !(pt->CHI == 256 && msplit_supported(N2, pt->CHI, n_out)))
             return fail(PQD_ERR_UNSUPPORTED, "N2=%d CHI=%d (chi 256: N2 4, 9 or 16 and at most 8 outputs)", N2, pt->CHI);
     }
     for (int t = 0; t < tr->n_traj; ++t) {
@@ -1685,6 +1723,65 @@ static int setup_hilbert(pqd_plan* P, const pqd_system* systems, const std::vect
     return PQD_OK;
 }
 
+// slices of the bond in flight in a free half step of lind_hilbert_pt.hip: as many as the thread bound (N^2 rounded up
+// to whole waves per slice), the LDS beside the nonzero lists (K and Kd once, R, T, Tn and nl_max B_k per slice) and chi
+// allow, then the fewest that keep the number of passes over the bond (no idle groups in the last pass); cap > 0
+// bounds it (PQD_HBPT_G). Speed only: a slice's arithmetic does not depend on it
+static int hilbert_pt_groups(int N, int nl_max, int chi, int csr_lds, int cap) {
+    const int nt1 = (N * N + 63) / 64 * 64;
+    int G = std::min(HBPT_NT_MAX / nt1, chi);
+    while (G > 1 && hbpt_mat_elems(N, nl_max, G) * sizeof(double2) + csr_lds > (size_t)HBPT_LDS_MAX) --G;
+    if (cap > 0) G = std::min(G, cap);
+    G = std::max(G, 1);
+    const int passes = (chi + G - 1) / G;
+    return (chi + passes - 1) / passes;
+}
+
+// The PT side of a plan on the Hilbert-space path with a wide PT: the schedule, the bond workspace, the elements
+// ordered by dictionary entry in units of HBPT_EB, G and the LDS tile (lind_hilbert_pt.hip)
+static int setup_hilbert_pt(pqd_plan* P, const pqd_pt* pt, const std::vector<int32_t>& sch, const PlanEnv& env,
+                            hipStream_t s) {
+    const int N = P->hp.N, NN = N * N, chi = pt->chi;
+    std::vector<int> ug, uel;
+    for (int g = 0; g < pt->D; ++g) {
+        int fill = HBPT_EB;
+        for (int a = 0; a < NN; ++a) {
+            if (pt->gmap_h[a] != g) continue;
+            if (fill == HBPT_EB) {
+                ug.push_back(g);
+                uel.insert(uel.end(), HBPT_EB, -1);
+                fill = 0;
+            }
+            uel[uel.size() - HBPT_EB + fill++] = a;
+        }
+    }
+    const int n_units = (int)ug.size();
+    HilbertPtParams& hq = P->hq;
+    hq.h = P->hp;
+    hq.chi = chi; hq.D = pt->D;
+    hq.G = hilbert_pt_groups(N, P->hp.nl_max, chi, P->hp.csr_lds, env.hbpt_g);
+    // the tile: the units that fit the LDS the matrices take anyway (one unit where that is more: chi = 256 is 33 KB)
+    const size_t cap_elems = ((size_t)HBPT_LDS_MAX - P->hp.csr_lds) / sizeof(double2);
+    const size_t mat = hbpt_mat_elems(N, P->hp.nl_max, hq.G), unit = hbpt_unit_elems(chi);
+    size_t ut = std::max<size_t>(1, mat / unit);
+    ut = std::min<size_t>({ut, cap_elems / unit, (size_t)n_units});
+    if (ut < 1) return fail(PQD_ERR_UNSUPPORTED, "chi %d: a PT unit does not fit the LDS beside the nonzero lists", chi);
+    hq.ut = (int)ut;
+    hq.lds_elems = (int)std::max(mat, ut * unit);
+    hq.n_units = n_units;
+    HIPCHK(P->sched.upload(sch.data(), sch.size(), s));
+    HIPCHK(P->hq_unit_g.upload(ug.data(), ug.size(), s));
+    HIPCHK(P->hq_unit_el.upload(uel.data(), uel.size(), s));
+    const size_t xn = std::max<size_t>(1, (size_t)P->n_traj * chi * NN);
+    if (hipError_t e = P->hq_X.alloc(xn); e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? PQD_ERR_NOMEM : PQD_ERR_HIP, "bond workspace of %zu bytes: %s",
+                    xn * sizeof(double2), hipGetErrorString(e));
+    hq.Q = pt->Q.p; hq.closure = pt->closure.p; hq.closure0 = pt->closure0.p; hq.bond0 = pt->bond0.p;
+    hq.sched = P->sched.p; hq.X = P->hq_X.p; hq.unit_g = P->hq_unit_g.p; hq.unit_el = P->hq_unit_el.p;
+    HIPCHK(hipStreamSynchronize(s));  // the uploads read host vectors of this frame
+    return PQD_OK;
+}
+
 int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, const int32_t* traj_sys,
                           const pqd_grid* grid, const pqd_pt* pt, const int32_t* sched, const pqd_c128* rho0,
                           int32_t n_out, const pqd_c128* out_ops, const pqd_traj* tr, int64_t out_len,
@@ -1719,6 +1816,14 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
     if (!pt && (N > 6 || (env.hilbert && hb_fits))) {
         P->hilbert = true;
         if ((rc = setup_hilbert(P, systems, tsys, grid, rho0, out_ops, tr, s))) return rc;
+        *out = guard.release();
+        return PQD_OK;
+    }
+    if (pt && pt->wide) {  // the same inputs, then the bond workspace and the PT units (lind_hilbert_pt.hip)
+        P->hilbert = true;
+        P->hilbert_pt = true;
+        if ((rc = setup_hilbert(P, systems, tsys, grid, rho0, out_ops, tr, s))) return rc;
+        if ((rc = setup_hilbert_pt(P, pt, sch, env, s))) return rc;
         *out = guard.release();
         return PQD_OK;
     }
@@ -1772,7 +1877,10 @@ int pqd_plan_execute(pqd_plan* P, int32_t rebuild_free) {
     HIPCHK(hipEventRecord(e[0], s));
     if (P->hilbert) {  // one kernel, no free propagators to rebuild
         HIPCHK(hipEventRecord(e[1], s));
-        HIPCHK(launch_hilbert(P->n_traj, P->hp, s));
+        if (P->hilbert_pt)
+            HIPCHK(launch_hilbert_pt(P->n_traj, P->hq, s));
+        else
+            HIPCHK(launch_hilbert(P->n_traj, P->hp, s));
         HIPCHK(hipEventRecord(e[2], s));
         P->ev_head = (P->ev_head + 1) % pqd_plan::RING;
         P->ev_count++;
@@ -1972,7 +2080,7 @@ int pqd_plan_sweep_readout(const pqd_plan* P, int32_t* on) {
 }
 
 static int plan_path(const pqd_plan* P) {
-    return P->hilbert ? PQD_PATH_HILBERT : P->nopt ? PQD_PATH_NOPT : P->split ? PQD_PATH_SPLIT : P->msplit ? PQD_PATH_MSPLIT
+    return P->hilbert_pt ? PQD_PATH_HILBERT_PT : P->hilbert ? PQD_PATH_HILBERT : P->nopt ? PQD_PATH_NOPT : P->split ? PQD_PATH_SPLIT : P->msplit ? PQD_PATH_MSPLIT
          : P->quad ? PQD_PATH_QUAD : PQD_PATH_BATCHED;
 }
 

@@ -128,16 +128,18 @@ class ProcessTensor:
         s = np.where(n < self.n_init, n, self.n_init + (n - self.n_init) % per)
         return np.ascontiguousarray(np.minimum(s, self.n_slices - 1), dtype=np.int32)
 
-    def handle(self, ctx, dim):
-        """device-resident copy (uploaded once per context, shared by all calls)"""
-        key = (id(ctx), dim)
+    def handle(self, ctx, dim, wide=False):
+        """device-resident copy (uploaded once per context, shared by all calls). wide=True: the handle of
+        pqd_pt_create_wide (dim 2..24), which sends a plan onto the Hilbert-space path with a PT"""
+        key = (id(ctx), dim, bool(wide))
         if key not in self._handles:
             d = _lib.pqd_pt_desc()
             d.chi, d.D, d.n_slices = self.chi, self.D, self.n_slices
             d.Q, d.closure, d.closure0 = _lib.cptr(self.Q), _lib.cptr(self.closure), _lib.cptr(self.closure0)
             d.bond0, d.gmap = _lib.cptr(self.bond0), _lib.iptr(self.gmap)
             h = C.c_void_p()
-            _lib.check(_lib.lib().pqd_pt_create(ctx.handle, int(dim), C.byref(d), C.byref(h)))
+            create = _lib.lib().pqd_pt_create_wide if wide else _lib.lib().pqd_pt_create
+            _lib.check(create(ctx.handle, int(dim), C.byref(d), C.byref(h)))
             self._handles[key] = (h, ctx)
         return self._handles[key][0]
 
@@ -211,7 +213,7 @@ def _systems(system):
     return list(system) if isinstance(system, (list, tuple)) else [system]
 
 
-def _prep(system, grid, rho0, out_ops, traj, pt, ctx):
+def _prep(system, grid, rho0, out_ops, traj, pt, ctx, wide_pt=False):
     systems = _systems(system)
     N = systems[0].dim
     if any(s.dim != N for s in systems):
@@ -232,7 +234,7 @@ def _prep(system, grid, rho0, out_ops, traj, pt, ctx):
             # a PT is a discretisation at its own dt (the eta_k are integrals over dt-wide slices): propagating it
             # on another grid is wrong physics, not a numerical detail
             raise ValueError(f"PT was generated for dt = {pt.dt}, the grid has dt = {grid.dt}")
-        pth = pt.handle(ctx, N)
+        pth = pt.handle(ctx, N, wide_pt)
         sched = pt.schedule(max(1, grid.n_steps))
     tsys = np.ascontiguousarray(np.zeros(max(1, traj.n_traj)) if traj.system is None else traj.system, dtype=np.int32)
     if len(systems) == 1 and traj.system is not None and np.any(tsys != 0):
@@ -242,16 +244,19 @@ def _prep(system, grid, rho0, out_ops, traj, pt, ctx):
 
 
 def propagate(system, grid: Grid, rho0, out_ops: Sequence, traj: Trajectories,
-              pt: Optional[ProcessTensor] = None, ctx=None):
+              pt: Optional[ProcessTensor] = None, ctx=None, *, wide_pt=False):
     """Run all trajectories; returns a list of (window_len, n_out) complex arrays.
-    `system` may be a list of Systems (parameter scan); traj.system then selects one per trajectory."""
+    `system` may be a list of Systems (parameter scan); traj.system then selects one per trajectory.
+    wide_pt=True (here, in propagate_table, propagate_trapz and Plan) hands the PT over as a wide handle
+    (pqd_pt_create_wide): the run takes the Hilbert-space path with a PT, at any dim in [2, 24]. Without it a PT
+    needs dim <= 6, as before."""
     ctx = ctx or _lib.context()
     dim = _systems(system)[0].dim
     with ctx.lock:
-        keep, total = _prep(system, grid, rho0, out_ops, traj, pt, ctx)
+        keep, total = _prep(system, grid, rho0, out_ops, traj, pt, ctx, wide_pt)
         k1, k2, r0, ops, sched, sc, gc, tc, tsys, n_sys = keep
         out = np.zeros(max(1, total), dtype=np.complex128)
-        pth = pt.handle(ctx, dim) if pt is not None else None
+        pth = pt.handle(ctx, dim, wide_pt) if pt is not None else None
         _lib.check(_lib.lib().pqd_propagate_multi(ctx.handle, n_sys, sc, _lib.iptr(tsys), C.byref(gc), pth,
                                                   _lib.iptr(sched), _lib.cptr(r0), len(out_ops), _lib.cptr(ops),
                                                   C.byref(tc), _lib.cptr(out), max(1, total)))
@@ -285,7 +290,7 @@ def tables_from_outputs(outs, traj: Trajectories, grid: Grid):
 
 
 def propagate_trapz(system, grid: Grid, rho0, out_ops: Sequence, traj: Trajectories, k_head, k_tail, dx,
-                    pt: Optional[ProcessTensor] = None, ctx=None):
+                    pt: Optional[ProcessTensor] = None, ctx=None, *, wide_pt=False):
     """propagate() reduced on the device to trapezoid integrals over each trajectory's output window
     (pqd_propagate_trapz): res[t, q] = dx (y_{k_head[q]}(0) / 2 + sum_{s=1}^{L-2} y_{k_tail[q]}(s) + y_{k_tail[q]}(L-1) / 2),
     0 for windows shorter than 2 steps. The tau integrals of G2_reuse (pol_entanglement/G2.py:484-505) without
@@ -298,9 +303,9 @@ def propagate_trapz(system, grid: Grid, rho0, out_ops: Sequence, traj: Trajector
         raise ValueError("k_head and k_tail must be 1-D of equal length")
     res = np.zeros((max(1, traj.n_traj), max(1, len(kh))), dtype=np.complex128)
     with ctx.lock:
-        keep, total = _prep(system, grid, rho0, out_ops, traj, pt, ctx)
+        keep, total = _prep(system, grid, rho0, out_ops, traj, pt, ctx, wide_pt)
         k1, k2, r0, ops, sched, sc, gc, tc, tsys, n_sys = keep
-        pth = pt.handle(ctx, dim) if pt is not None else None
+        pth = pt.handle(ctx, dim, wide_pt) if pt is not None else None
         _lib.check(_lib.lib().pqd_propagate_trapz(ctx.handle, n_sys, sc, _lib.iptr(tsys), C.byref(gc), pth,
                                                   _lib.iptr(sched), _lib.cptr(r0), len(out_ops), _lib.cptr(ops),
                                                   C.byref(tc), len(kh), _lib.iptr(kh), _lib.iptr(kt), float(dx),
@@ -309,7 +314,7 @@ def propagate_trapz(system, grid: Grid, rho0, out_ops: Sequence, traj: Trajector
 
 
 def propagate_table(system, grid: Grid, rho0, out_ops: Sequence, traj: Trajectories,
-                    pt: Optional[ProcessTensor] = None, ctx=None):
+                    pt: Optional[ProcessTensor] = None, ctx=None, *, wide_pt=False):
     """propagate() returning ACE's output table per trajectory: (1 + n_out, window_len) arrays, row 0 = the step
     times grid.ta + dt * step, row 1 + k = output k (general_system.py:343), assembled on the device
     (pqd_propagate_table) so the arrays are views of one host buffer."""
@@ -318,10 +323,10 @@ def propagate_table(system, grid: Grid, rho0, out_ops: Sequence, traj: Trajector
     off, _ = table_offsets(traj, len(out_ops))
     n_tab = int(off[-1])
     with ctx.lock:
-        keep, total = _prep(system, grid, rho0, out_ops, traj, pt, ctx)
+        keep, total = _prep(system, grid, rho0, out_ops, traj, pt, ctx, wide_pt)
         k1, k2, r0, ops, sched, sc, gc, tc, tsys, n_sys = keep
         table = np.empty(max(1, n_tab), dtype=np.complex128)
-        pth = pt.handle(ctx, dim) if pt is not None else None
+        pth = pt.handle(ctx, dim, wide_pt) if pt is not None else None
         _lib.check(_lib.lib().pqd_propagate_table(ctx.handle, n_sys, sc, _lib.iptr(tsys), C.byref(gc), pth,
                                                   _lib.iptr(sched), _lib.cptr(r0), len(out_ops), _lib.cptr(ops),
                                                   C.byref(tc), _lib.cptr(table), max(1, n_tab)))
@@ -407,15 +412,15 @@ def dressed_table(times, evals, evecs):
 class Plan:
     """Device-resident propagation job for repeated execution (bench.py, parameter scans)."""
 
-    def __init__(self, system, grid, rho0, out_ops, traj, pt=None, ctx=None):
+    def __init__(self, system, grid, rho0, out_ops, traj, pt=None, ctx=None, *, wide_pt=False):
         self.ctx = ctx or _lib.context()
         self.traj = traj
         self.n_out = len(out_ops)
         self.dim = _systems(system)[0].dim
         with self.ctx.lock:
-            self._keep, self.total = _prep(system, grid, rho0, out_ops, traj, pt, self.ctx)
+            self._keep, self.total = _prep(system, grid, rho0, out_ops, traj, pt, self.ctx, wide_pt)
             k1, k2, r0, ops, sched, sc, gc, tc, tsys, n_sys = self._keep
-            pth = pt.handle(self.ctx, self.dim) if pt is not None else None
+            pth = pt.handle(self.ctx, self.dim, wide_pt) if pt is not None else None
             h = C.c_void_p()
             _lib.check(_lib.lib().pqd_plan_create_multi(self.ctx.handle, n_sys, sc, _lib.iptr(tsys), C.byref(gc),
                                                         pth, _lib.iptr(sched), _lib.cptr(r0), self.n_out,
@@ -434,7 +439,8 @@ class Plan:
 
     PATHS = {0: "no PT (one wave per trajectory)", 1: "batched lock-step sweep", 2: "split groups",
              3: "register-resident TLS quads", 4: "split groups, several trajectories per group",
-             5: "no PT, Hilbert space (one workgroup per trajectory)"}
+             5: "no PT, Hilbert space (one workgroup per trajectory)",
+             6: "wide PT, Hilbert space (one workgroup per trajectory, bond slices in a workspace)"}
 
     def info(self):
         """(path name, trajectories per workgroup, split launches that fell back to the batched kernel)"""

@@ -242,7 +242,8 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
                       prepare_only=False, LO_params=None, dressedstates=False, rf_op=None, rf_file=None,
                       firstonly=False, J_to_file=None, J_file=None, factor_ah=None, use_infinite=False,
                       print_H=False, calc_dynmap=False, rho0=None, get_M_t=None, trajectories=None, n_sub=1,
-                      device=None, pulse_sampling="ace_file", trapz=None, dressed_rho=None, lower_only=False):
+                      device=None, pulse_sampling="ace_file", trapz=None, dressed_rho=None, lower_only=False,
+                      wide_pt=None):
     """Propagate one trajectory (or a batch: `trajectories`) and return ACE's output table.
 
     Returns (1 + len(output_ops), n_t) complex, row 0 = time (general_system.py:104-110, 343).
@@ -271,6 +272,11 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
     Systems (one per distinct drive and generator), each trajectory's system index, the output grid and each
     trajectory's output count. No device is touched and no PT is resolved; the dim > 6 refusals hold as without it.
     The dressed-state functions take H(t) of the cavity and sensor models from it (general_dressed_states.py).
+
+    wide_pt=True opts in to phonons above dim 6 (dim <= 24: the cavity and sensor models): the PT is resolved as for
+    dim <= 6 and the run takes the Hilbert-space path with a PT (engine.propagate(..., wide_pt=True)). None (default)
+    lets the environment switch PQD_WIDE_PT=1 decide, for scripts that cannot change their call sites; False never
+    opts in. Without the opt-in phonons above dim 6 are refused as before; at dim <= 6 nothing changes either way.
     """
     if pulse_sampling not in ("exact", "ace_file"):
         raise ValueError(f"pulse_sampling must be 'exact' or 'ace_file', not {pulse_sampling!r}")
@@ -301,15 +307,22 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
     if dim is None:
         dim = 2  # "assuming TLS" (:19)
     mat = lambda s: opgrammar.to_matrix(s, dim)  # noqa: E731
+    wide = (os.environ.get("PQD_WIDE_PT") == "1") if wide_pt is None else bool(wide_pt)
     if dim > 6:
-        # above dim 6 only the propagation without PT exists (the Hilbert-space kernel, dim <= 24): everything that
-        # builds N^2 x N^2 superoperators stops at 6. Refused here, before a PT is generated or read
+        # above dim 6 the propagation runs in Hilbert space (dim <= 24): without a PT, or with one under the wide_pt
+        # opt-in. Everything that builds N^2 x N^2 superoperators stops at 6. Refused here, before a PT is generated
+        # or read
         from .._lib import HILBERT_MAX_DIM
-        for name, on in (("phonons=True", phonons), ("calc_dynmap", calc_dynmap), ("get_M_t", get_M_t is not None),
-                         ("dressedstates", dressedstates)):
+        wide = wide and dim <= HILBERT_MAX_DIM
+        for name, on in (("phonons=True", phonons and not wide), ("calc_dynmap", calc_dynmap),
+                         ("get_M_t", get_M_t is not None), ("dressedstates", dressedstates)):
             if on:
+                hint = "; wide_pt=True or PQD_WIDE_PT=1 propagates it with phonons" \
+                    if name == "phonons=True" and dim <= HILBERT_MAX_DIM else ""
                 raise NotImplementedError(f"{name} needs dim <= 6, this system has dim {dim} (without it a system "
-                                          f"of dim <= {HILBERT_MAX_DIM} propagates)")
+                                          f"of dim <= {HILBERT_MAX_DIM} propagates{hint})")
+    # engine.* receive wide_pt only where it applies: a PT above dim 6 under the opt-in
+    wide_kw = {"wide_pt": True} if (wide and phonons and dim > 6) else {}
 
     def hamiltonian(ops):
         H = np.zeros((dim, dim), dtype=complex)
@@ -489,14 +502,15 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
             raise ValueError("trapz needs output_ops")
         k_head, k_tail, dx = trapz
         res = propagate_trapz(systems if multi else system, grid, rho_init, out_mats, tr, k_head, k_tail, dx, pt=pt,
-                              ctx=_lib.context(device))
+                              ctx=_lib.context(device), **wide_kw)
         return res if trajectories is not None else res[0]
     if n_real:
         # ACE's output table per trajectory, assembled on the device (pqd_propagate_table): views, no host copies
         res = propagate_table(systems if multi else system, grid, rho_init, out_mats, tr, pt=pt,
-                              ctx=_lib.context(device))
+                              ctx=_lib.context(device), **wide_kw)
         return res if trajectories is not None else res[0]
-    outs = propagate(systems if multi else system, grid, rho_init, out_mats, tr, pt=pt, ctx=_lib.context(device))
+    outs = propagate(systems if multi else system, grid, rho_init, out_mats, tr, pt=pt, ctx=_lib.context(device),
+                     **wide_kw)
     results = []
     for k, o in enumerate(outs):
         steps = np.arange(begins[k], ends[k] + 1)
