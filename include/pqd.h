@@ -277,6 +277,9 @@ void pqd_plan_destroy(pqd_plan* plan);
 /* ---- map-chain sweeps: reference Fortran signatures, hidden dims explicit, Fortran layouts ---- */
 int pqd_propagate_tau(pqd_ctx* ctx, const pqd_c128* dm_tl, int32_t n_maps, const pqd_c128* rho_init,
                       int32_t n_tau, int32_t dim, int32_t j_start, pqd_c128* rho_out);
+/* PQD_ERR_ARG when a trajectory would read a map past dm_tl(:, :, n_tfull - 1) (time_sparse beyond time, or
+ * j_i - 1 + n_tau > n_tfull - 1; the Fortran reads out of bounds there), on the blocked sweep and on the map-by-map
+ * kernels (PQD_MC_BLOCKED=0) alike */
 int pqd_calc_onetime_parallel(pqd_ctx* ctx, const pqd_c128* dm_tl, const pqd_c128* rho_init, int32_t n_tau,
                               int32_t n_t, int32_t n_tfull, int32_t dim, const pqd_c128* opA,
                               const pqd_c128* opB, const pqd_c128* opC, const double* time,
@@ -286,12 +289,18 @@ int pqd_calc_onetime_parallel_block(pqd_ctx* ctx, const pqd_c128* dm_block, cons
                                     int32_t n_t, int32_t n_tfull, int32_t dim, const pqd_c128* opA,
                                     const pqd_c128* opB, const pqd_c128* opC, const double* time,
                                     const double* time_sparse, pqd_c128* result);
+/* n_tauc = 0 is the Fortran's empty loop over the per-trajectory maps: dm_taucs2 is not read and may be NULL */
 int pqd_calc_twotime_phonon_block(pqd_ctx* ctx, const pqd_c128* dm_taucs2, const pqd_c128* dm_sep1,
                                   const pqd_c128* dm_sep2, const pqd_c128* dm_s, const pqd_c128* rho_init,
                                   int32_t n_tb, int32_t nx_tau, int32_t n_map, int32_t n_t, int32_t n_tfull,
                                   int32_t n_tauc, int32_t dim, const pqd_c128* opA, const pqd_c128* opB,
                                   const pqd_c128* opC, const double* time, const double* time_sparse,
                                   pqd_c128* result);
+/* The time-bin entry points (this one, _rows, pqd_four_time, pqd_dynamics_t1) propagate over the segments (0, t1_i),
+ * (t1_i, t1_j), (t1_j, tb) resp. (t1_i, t1_i+1) as propagate_tb does (timebin_tl.f90:50-77): n_map explicit maps, then
+ * one precalc map per set bit of the steps left. PQD_ERR_ARG, before anything is launched, when a segment the call
+ * reaches leaves 2^n_precalc steps or more (the Fortran reads past dm_tl_precalc; the reference's own
+ * n_precalc = int(log2(tb / dt)) + 1 never does for t1 <= tb) or applies explicit maps from a negative time */
 int pqd_four_time_8op(pqd_ctx* ctx, const pqd_c128* dm_1, const pqd_c128* dm_2, const pqd_c128* rho_init,
                       const double* t1, const pqd_c128* precalc, int32_t n_t, double dt, int32_t n_map,
                       int32_t dim, const pqd_c128* ops8, int32_t early_only, int32_t late_t1_only, double tb,

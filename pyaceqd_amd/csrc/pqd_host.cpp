@@ -2204,7 +2204,7 @@ static int mapchain_run(pqd_ctx* ctx, MapChainParams& p, const pqd_c128* dmA, si
                    (N2 == 4 || N2 == 9 || N2 == 16 || N2 == 25 || N2 == 36);
     std::vector<int> pos;
     int pmax = 0;
-    if (blocked) {
+    if (p.mode == 0 || blocked) {
         pos.resize(p.n_t);
         int j = 1;
         for (int i = 0; i < p.n_t; ++i) {
@@ -2212,29 +2212,30 @@ static int mapchain_run(pqd_ctx* ctx, MapChainParams& p, const pqd_c128* dmA, si
             pos[i] = j - 1;
             pmax = std::max(pmax, j - 1);
         }
-        if (p.mode == 1) {
-            // a trunk that ends past the first period (j > n_tb) never wraps in the tau loop (:270-287: jj resets
-            // only when it equals n_tb + 1), so that trajectory applies dm_s at every tau step: it starts at q_s, the
-            // first position of a constant dm_s region placed after the periodic positions (map_at)
-            int qp = 0;
-            bool any_s = false;
-            for (int i = 0; i < p.n_t; ++i) {
-                if (pos[i] + 1 <= p.n_tb) qp = std::max(qp, pos[i] + p.n_tau);
-                else any_s = true;
-            }
-            p.q_s = any_s ? qp : INT_MAX;
-            for (int i = 0; i < p.n_t; ++i)
-                if (pos[i] + 1 > p.n_tb) pos[i] = p.q_s;
-            // precondition of that constant region: with n_map > n_tb a trunk ending at n_tb < j <= n_map walks
-            // dm_block(j), dm_block(j+1), ..., dm_block(n_map) before dm_s (:270-281), which the blocked position
-            // map does not represent; such calls run on the map-by-map kernels
-            if (any_s && p.n_map > p.n_tb) blocked = false;
+    }
+    // mode 0 reads dm_tl(:, :, j_i - 1 + n_tau) at its last tau step on either set of kernels
+    if (p.mode == 0 && (size_t)std::max(Q_of(pos, p.n_tau), pmax) > nA)
+        return fail(PQD_ERR_ARG, "the sweep would read map %d of %zu (time_sparse beyond time, or n_tau too long "
+                    "for dm_tl)", std::max(Q_of(pos, p.n_tau), pmax), nA);
+    if (blocked && p.mode == 1) {
+        // a trunk that ends past the first period (j > n_tb) never wraps in the tau loop (:270-287: jj resets
+        // only when it equals n_tb + 1), so that trajectory applies dm_s at every tau step: it starts at q_s, the
+        // first position of a constant dm_s region placed after the periodic positions (map_at)
+        int qp = 0;
+        bool any_s = false;
+        for (int i = 0; i < p.n_t; ++i) {
+            if (pos[i] + 1 <= p.n_tb) qp = std::max(qp, pos[i] + p.n_tau);
+            else any_s = true;
         }
+        p.q_s = any_s ? qp : INT_MAX;
+        for (int i = 0; i < p.n_t; ++i)
+            if (pos[i] + 1 > p.n_tb) pos[i] = p.q_s;
+        // precondition of that constant region: with n_map > n_tb a trunk ending at n_tb < j <= n_map walks
+        // dm_block(j), dm_block(j+1), ..., dm_block(n_map) before dm_s (:270-281), which the blocked position
+        // map does not represent; such calls run on the map-by-map kernels
+        if (any_s && p.n_map > p.n_tb) blocked = false;
     }
     if (blocked) {
-        if (p.mode == 0 && (size_t)std::max(Q_of(pos, p.n_tau), pmax) > nA)
-            return fail(PQD_ERR_ARG, "the sweep would read map %d of %zu (time_sparse beyond time, or n_tau too long "
-                        "for dm_tl)", std::max(Q_of(pos, p.n_tau), pmax), nA);
         const int Q = Q_of(pos, p.n_tau);
         const char* el = getenv("PQD_MC_L");
         int L = el ? atoi(el) : (int)std::lround(std::sqrt((double)std::max(1, p.n_tau)));
@@ -2359,14 +2360,15 @@ int pqd_calc_twotime_phonon_block(pqd_ctx* ctx, const pqd_c128* dm_taucs2, const
                                   int32_t n_tauc, int32_t dim, const pqd_c128* opA, const pqd_c128* opB,
                                   const pqd_c128* opC, const double* time, const double* time_sparse,
                                   pqd_c128* result) {
-    if (!dm_taucs2 || !dm_sep2 || !dm_s) return fail(PQD_ERR_ARG, "NULL map argument");
     if (n_map < 1 || n_tb < 1 || nx_tau < 0 || n_tauc < 0) return fail(PQD_ERR_ARG, "bad block sizes");
+    // n_tauc = 0: the loop over the per-trajectory maps is empty (:466), dm_taucs2 has no element and is not read
+    if ((n_tauc > 0 && !dm_taucs2) || !dm_sep2 || !dm_s) return fail(PQD_ERR_ARG, "NULL map argument");
     if (n_tauc > n_t) return fail(PQD_ERR_ARG, "n_tauc %d > n_t %d (reads past rho_buffer in the reference)", n_tauc, n_t);
     MapChainParams p{};
     p.mode = 2; p.dim = dim; p.n_t = n_t; p.n_tfull = n_tfull; p.n_tau = n_tb * nx_tau;
     p.n_map = n_map; p.n_tb = n_tb; p.nx_tau = nx_tau; p.n_tauc = n_tauc;
-    return mapchain_run(ctx, p, dm_sep1, n_map, dm_sep2, n_map, dm_taucs2, (size_t)std::max(1, n_tauc) * n_map, dm_s,
-                        rho_init, opA, opB, opC, time, time_sparse, result);
+    return mapchain_run(ctx, p, dm_sep1, n_map, dm_sep2, n_map, n_tauc > 0 ? dm_taucs2 : nullptr,
+                        (size_t)n_tauc * n_map, dm_s, rho_init, opA, opB, opC, time, time_sparse, result);
 }
 
 int pqd_propagate_tau(pqd_ctx* ctx, const pqd_c128* dm_tl, int32_t n_maps, const pqd_c128* rho_init,
@@ -2407,6 +2409,23 @@ int pqd_map_tail(pqd_ctx* ctx, const pqd_c128* M, int32_t N2, const pqd_c128* X,
     return PQD_OK;
 }
 
+// propagate_tb's step counts (timebin_tl.f90:59-62, as prop_tb in mapchain.hip takes them): the steps left to the binary
+// powers after the explicit maps, or -1 for a segment that indexes the explicit maps below 1 or whose counts do not
+// fit an int
+static long long tb_remainder(double ts, double te, double dt, int n_dm) {
+    const double qs = (double)llround(ts * 1000000.0) / 1000000.0 / dt;
+    const double qe = (double)llround(te * 1000000.0) / 1000000.0 / dt;
+    if (!(std::fabs(qs) < 1e9) || !(std::fabs(qe) < 1e9)) return -1;
+    const int n_start = (int)qs, n_stop = (int)qe;
+    int n_steps = n_stop - n_start;
+    const int steps_dm = std::min(n_dm - n_start, n_steps);
+    if (steps_dm > 0) {
+        if (n_start < 0) return -1;
+        n_steps -= steps_dm;
+    }
+    return std::max(n_steps, 0);
+}
+
 static int four_time_common(pqd_ctx* ctx, FourTimeParams& p, const pqd_c128* dm_1, const pqd_c128* dm_2,
                             const pqd_c128* rho_init, const double* t1, const pqd_c128* precalc, const pqd_c128* ops,
                             int n_ops, pqd_c128* result, bool dyn, int row_lo = 0, int row_hi = INT_MAX) {
@@ -2414,6 +2433,33 @@ static int four_time_common(pqd_ctx* ctx, FourTimeParams& p, const pqd_c128* dm_
         return fail(PQD_ERR_ARG, "NULL argument");
     if (p.dim < 2 || p.dim > 6) return fail(PQD_ERR_UNSUPPORTED, "dim %d", p.dim);
     if (p.n_t < 1 || p.n_map < 1 || p.n_precalc < 1 || !(p.dt > 0)) return fail(PQD_ERR_ARG, "bad sizes");
+    {
+        // every segment the call propagates over: fast_propagate (timebin_tl.f90:36-46) reads dm_tl_precalc(:, :, bit + 1)
+        // for every set bit of the remainder, past the array when the remainder reaches 2^n_precalc; the kernels
+        // stop at n_precalc, so such a call is refused rather than answered with steps dropped
+        const long long lim = p.n_precalc < 31 ? (1LL << p.n_precalc) : (1LL << 31);
+        auto bad = [&](double ts, double te) {
+            const long long r = tb_remainder(ts, te, p.dt, p.n_map);
+            if (r >= 0 && r < lim) return 0;
+            if (r < 0)
+                return fail(PQD_ERR_ARG, "segment (%g, %g) starts before the first map or is too long for dt %g", ts, te,
+                            p.dt);
+            return fail(PQD_ERR_ARG, "segment (%g, %g) leaves %lld steps after the %d explicit maps: needs precalc "
+                        "map %d of %d", ts, te, r, p.n_map, 64 - __builtin_clzll((unsigned long long)r), p.n_precalc);
+        };
+        int rc = 0;
+        if (dyn) {
+            for (int i = 0; i + 1 < p.n_t && !rc; ++i) rc = bad(t1[i], t1[i + 1]);
+        } else {
+            const bool to_tb = p.variant != 0 || !p.early_only;  // (t2, tb) is not reached under early_only
+            for (int i = 0; i < p.n_t && !rc; ++i) {
+                rc = bad(0.0, t1[i]);
+                if (!rc && to_tb) rc = bad(t1[i], p.tb);
+                for (int j = i; j < p.n_t && !rc; ++j) rc = bad(t1[i], t1[j]);
+            }
+        }
+        if (rc) return rc;
+    }
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const int N2 = p.dim * p.dim;

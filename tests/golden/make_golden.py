@@ -137,6 +137,35 @@ def gen_fortran():
                             result8_late=np.asarray(res8l), result4=np.asarray(res4), dyn_t1=np.asarray(dyn))
 
 
+def gen_timebin_extra():
+    """timebin_tl at the dims gen_fortran leaves out: 3 (7 pairs packed per wave, one padding lane) and 6 (one pair per
+    wave). A generator of its own so that the files gen_fortran writes keep their bytes. Dim 6 is kept small (6 maps,
+    5 points): the file holds 2 * 6 + 5 maps of 36 x 36."""
+    for dim, n_map, t1 in ((3, 12, np.array([0.0, 0.1, 0.3, 0.6, 0.7, 1.0, 1.4, 2.0, 2.5])),
+                           (6, 6, np.array([0.0, 0.3, 0.65, 1.4, 2.5]))):
+        rng = np.random.default_rng(2000 + dim)
+        N2 = dim * dim
+        dt, tb = 0.1, 3.0
+        dm_1 = rand_lindblad_maps(n_map, dim, dt, rng)
+        dm_2 = rand_lindblad_maps(n_map, dim, dt, rng)
+        tl = rand_lindblad_maps(1, dim, dt, rng)[0]
+        n_precalc = int(np.log2(tb / dt)) + 1  # twophoton_new.py:606
+        precalc = np.stack([np.linalg.matrix_power(tl, 2 ** k) for k in range(n_precalc)])
+        dm_1c = np.conj(dm_1); dm_2c = np.conj(dm_2); prec_c = np.conj(precalc)  # twophoton_new.py:114-116
+        rho0 = rand_rho(dim, rng).reshape(N2)
+        ops8 = [rand_op(dim, rng) for _ in range(8)]
+        a = (F(dm_1c), F(dm_2c), rho0, t1, F(prec_c), dt, dim)
+        res8 = fref.four_time_8op(*a, ops8, False, False, tb)
+        res8e = fref.four_time_8op(*a, ops8, True, False, tb)
+        res8l = fref.four_time_8op(*a, ops8, False, True, tb)
+        res4 = fref.four_time(*a, ops8[0], ops8[1], ops8[2], ops8[3], tb)
+        dyn = fref.dynamics_t1(*a, tb)
+        savez_lzma(os.path.join(HERE, f"fortran_timebin_d{dim}.npz"),
+                   dm_1=dm_1c, dm_2=dm_2c, precalc=prec_c, rho_init=rho0, t1=t1, dt=dt, tb=tb,
+                   ops8=np.stack(ops8), result8=np.asarray(res8), result8_early=np.asarray(res8e),
+                   result8_late=np.asarray(res8l), result4=np.asarray(res4), dyn_t1=np.asarray(dyn))
+
+
 def gen_pyref():
     sys.path.insert(0, REF_ROOT)
     from pyaceqd import pulses as P  # noqa: E402
@@ -611,6 +640,7 @@ if __name__ == "__main__":
     if not fref.available():
         raise SystemExit("build oracle/_ref first: make -C oracle ref")
     gen_fortran()
+    gen_timebin_extra()
     gen_pyref()
     gen_correlations()
     gen_correlations_phonons()

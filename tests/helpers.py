@@ -160,6 +160,173 @@ def numpy_propagate(sysd, grid, rho0, out_ops, traj, pt=None):
     return res
 
 
+# ------------------------------------------------------------------ timebin_tl.f90 restated in long double
+# Written from the Fortran (timebin/timebin_tl.f90:13-77, :145-342), not from the C oracle: an independent check of
+# oracle/mapchain_oracle.c. Map stacks in the Fortran layout (N2, N2, n), vectors column-major vec(rho). Time and
+# index arithmetic stays in float64 (it decides the step counts); states and maps are np.clongdouble. Every function
+# also returns the highest index (0-based) of a precalc map it used, -1 when it used none.
+LD = np.clongdouble
+
+
+def tb_round6(x):
+    """round_to_6 (:13-20): nint(x * 10^6) / 10^6, nint rounding halves away from zero"""
+    v = float(x) * 1000000.0
+    n = int(np.floor(abs(v) + 0.5))
+    return float(n if v >= 0 else -n) / 1000000.0
+
+
+def tb_steps(t_start, t_stop, dt, n_dm):
+    """(n_start, steps on the explicit maps, steps left to fast_propagate) of propagate_tb (:59-75)"""
+    n_start = int(tb_round6(t_start) / dt)
+    n_stop = int(tb_round6(t_stop) / dt)
+    n_steps = n_stop - n_start
+    steps_dm = max(0, min(n_dm - n_start, n_steps))
+    return n_start, steps_dm, max(0, n_steps - steps_dm)
+
+
+def numpy_fast_propagate(rho, precalc, n_steps):
+    """fast_propagate (:23-47): one precalc map per set bit of n_steps, least significant first"""
+    rho = np.asarray(rho, dtype=LD)
+    n, i, top = int(n_steps), 0, -1
+    while n > 0:
+        if n & 1:
+            rho = np.asarray(precalc[:, :, i], dtype=LD) @ rho
+            top = i
+        n >>= 1
+        i += 1
+    return rho, top
+
+
+def numpy_propagate_tb(t_start, t_stop, dt, rho, dm_tl, precalc):
+    """propagate_tb (:50-77): explicit maps dm_tl(:, :, n_start + 1 ...) while there are any, then fast_propagate"""
+    n_start, steps_dm, rem = tb_steps(t_start, t_stop, dt, dm_tl.shape[2])
+    rho = np.asarray(rho, dtype=LD)
+    for s in range(steps_dm):
+        rho = np.asarray(dm_tl[:, :, n_start + s], dtype=LD) @ rho
+    top = -1
+    if rem > 0:
+        rho, top = numpy_fast_propagate(rho, precalc, rem)
+    return rho, top
+
+
+def _tb_left(rho, op, dim):
+    return (np.asarray(op, dtype=LD) @ rho.reshape(dim, dim, order="F")).reshape(dim * dim, order="F")
+
+
+def _tb_right(rho, op, dim):
+    return (rho.reshape(dim, dim, order="F") @ np.asarray(op, dtype=LD)).reshape(dim * dim, order="F")
+
+
+def _tb_trace(rho, dim):
+    return np.trace(rho.reshape(dim, dim, order="F"))
+
+
+def numpy_four_time_8op(dm_1, dm_2, rho_init, t1, precalc, dt, dim, ops8, early_only, late_t1_only, tb):
+    """four_time_8op (:216-303); ops8 = (et1l, et1r, et2l, et2r, lt1l, lt1r, lt2l, lt2r)"""
+    dm_1, dm_2, precalc = (np.asarray(a, dtype=LD) for a in (dm_1, dm_2, precalc))
+    et1l, et1r, et2l, et2r, lt1l, lt1r, lt2l, lt2r = (np.asarray(o, dtype=LD) for o in ops8)
+    n_t = len(t1)
+    res = np.zeros((n_t, n_t), dtype=LD)
+    tops = [-1]
+
+    def prop(a, b, r, dm):
+        r, top = numpy_propagate_tb(a, b, dt, r, dm, precalc)
+        tops.append(top)
+        return r
+    for i in range(n_t):
+        t1n = t1[i]
+        rho_vec = prop(0.0, t1n, np.asarray(rho_init, dtype=LD), dm_1)
+        for j in range(n_t - i):
+            t2 = t1[i + j]
+            r = _tb_left(_tb_right(rho_vec, et1r, dim), et1l, dim)
+            r = prop(t1n, t2, r, dm_1)
+            r = _tb_left(_tb_right(r, et2r, dim), et2l, dim)
+            if early_only:
+                res[i, i + j] = _tb_trace(r, dim)
+                continue
+            r = prop(t2, tb, r, dm_1)
+            r = prop(0.0, t1n, r, dm_2)
+            r = _tb_left(_tb_right(r, lt1r, dim), lt1l, dim)
+            if late_t1_only:
+                res[i, i + j] = _tb_trace(r, dim)
+                continue
+            r = prop(t1n, t2, r, dm_2)
+            r = _tb_left(_tb_right(r, lt2r, dim), lt2l, dim)
+            res[i, i + j] = _tb_trace(r, dim)
+    return res, max(tops)
+
+
+def numpy_four_time(dm_1, dm_2, rho_init, t1, precalc, dt, dim, ops4, tb):
+    """four_time (:145-214): op_1, op_2 from the right in the early bin, op_3, op_4 from the left in the late one"""
+    dm_1, dm_2, precalc = (np.asarray(a, dtype=LD) for a in (dm_1, dm_2, precalc))
+    o1, o2, o3, o4 = (np.asarray(o, dtype=LD) for o in ops4)
+    n_t = len(t1)
+    res = np.zeros((n_t, n_t), dtype=LD)
+    tops = [-1]
+
+    def prop(a, b, r, dm):
+        r, top = numpy_propagate_tb(a, b, dt, r, dm, precalc)
+        tops.append(top)
+        return r
+    for i in range(n_t):
+        t1n = t1[i]
+        rho_vec = prop(0.0, t1n, np.asarray(rho_init, dtype=LD), dm_1)
+        for j in range(n_t - i):
+            t2 = t1[i + j]
+            r = _tb_right(rho_vec, o1, dim)
+            r = prop(t1n, t2, r, dm_1)
+            r = _tb_right(r, o2, dim)
+            r = prop(t2, tb, r, dm_1)
+            r = prop(0.0, t1n, r, dm_2)
+            r = _tb_left(r, o3, dim)
+            r = prop(t1n, t2, r, dm_2)
+            r = _tb_left(r, o4, dim)
+            res[i, i + j] = _tb_trace(r, dim)
+    return res, max(tops)
+
+
+def numpy_dynamics_t1(dm_1, dm_2, rho_init, t1, precalc, dt, dim):
+    """dynamics_t1 (:305-342): column 0 = rho_init, columns 1 .. n_t - 1 along t1 with dm_1, then n_t - 1 more
+    along the same segments with dm_2, continuing from the last dm_1 column"""
+    dm_1, dm_2, precalc = (np.asarray(a, dtype=LD) for a in (dm_1, dm_2, precalc))
+    n_t = len(t1)
+    res = np.zeros((dim * dim, 2 * n_t - 1), dtype=LD)
+    res[:, 0] = np.asarray(rho_init, dtype=LD)
+    top = -1
+    for half, dm in enumerate((dm_1, dm_2)):
+        for i in range(n_t - 1):
+            k = i + half * (n_t - 1)
+            res[:, k + 1], tp = numpy_propagate_tb(t1[i], t1[i + 1], dt, res[:, k], dm, precalc)
+            top = max(top, tp)
+    return res, top
+
+
+def timebin_inputs(dim):
+    """seeded inputs of the time-bin tests: 7 explicit maps per bin, 5 binary powers of one map, dt = 0.1, tb = 2.3,
+    and per dim a sorted t1 grid sized so that the pair triangle leaves one pair in the last wave (dims 2-4), a ragged
+    last wave (dim 5) or exercises 28 padding lanes (dim 6); see tests/test_timebin_oracle.py for the properties"""
+    rng = np.random.default_rng(4200 + dim)
+    N2 = dim * dim
+    mk = lambda: np.eye(N2) + 0.05 * (rng.normal(size=(N2, N2)) + 1j * rng.normal(size=(N2, N2))) / dim  # noqa: E731
+    F = lambda maps: np.asfortranarray(np.asarray(maps).transpose(1, 2, 0))  # noqa: E731
+    n_map, n_precalc, dt, tb = 7, 5, 0.1, 2.3
+    dm_1 = F([mk() for _ in range(n_map)])
+    dm_2 = F([mk() for _ in range(n_map)])
+    tl = mk()
+    precalc = F([np.linalg.matrix_power(tl, 2 ** k) for k in range(n_precalc)])
+    rho = random_rho(dim, seed=4300 + dim).reshape(N2, order="F")
+    ops8 = [rng.normal(size=(dim, dim)) + 1j * rng.normal(size=(dim, dim)) for _ in range(8)]
+    t1 = {
+        2: np.sort(np.concatenate([np.round(np.arange(27) * 0.1, 6), [0.25, 0.3, 0.65, 1.25, 1.25, 2.05]])),
+        3: np.array([0.0, 0.1, 0.2, 0.25, 0.3, 0.3, 0.5, 0.6, 0.65, 0.7, 0.8, 1.2, 1.9, 2.3, 2.45]),
+        4: np.array([0.0, 0.1, 0.25, 0.3, 0.3, 0.65, 0.9, 1.7, 2.6]),
+        5: np.array([0.0, 0.25, 0.25, 0.6, 1.1, 2.5]),
+        6: np.array([0.25, 0.25, 0.6, 1.1, 2.5]),
+    }[dim]
+    return dict(dm_1=dm_1, dm_2=dm_2, rho=rho, t1=t1, precalc=precalc, dt=dt, dim=dim, ops8=ops8, tb=tb,
+                n_map=n_map, n_precalc=n_precalc)
+
+
 def simple_traj(n_steps, mtos=(), n_traj=1, begins=None, ends=None):
     begins = np.zeros(n_traj, dtype=int) if begins is None else np.asarray(begins)
     ends = np.full(n_traj, n_steps) if ends is None else np.asarray(ends)

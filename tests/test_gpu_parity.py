@@ -373,7 +373,7 @@ def test_mapchain_vs_fortran_golden(golden_dir, dim):
     assert rel(r, z["result"]) < 1e-12
 
 
-@pytest.mark.parametrize("dim", [2, 4, 5])
+@pytest.mark.parametrize("dim", [2, 3, 4, 5, 6])
 def test_timebin_vs_fortran_golden(golden_dir, dim):
     from pyaceqd_amd.timebin import timebin_tl as TB
     z = load(golden_dir, f"fortran_timebin_d{dim}.npz")
@@ -432,7 +432,7 @@ def test_mapchain_blocked_sweep_vs_oracle(monkeypatch, dim, L):
     assert rel(a, c) < 1e-11
 
 
-@pytest.mark.parametrize("dim", [2, 4, 6])
+@pytest.mark.parametrize("dim", [2, 3, 4, 5, 6])
 @pytest.mark.parametrize("L", ["8", "0"])
 @pytest.mark.parametrize("n_map", [7, 18])
 def test_mapchain_blocked_sweep_block_mode_vs_oracle(monkeypatch, dim, L, n_map):

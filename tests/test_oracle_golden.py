@@ -53,7 +53,7 @@ def test_calc_twotime_phonon_block(golden_dir, dim):
     assert rel(r, z["result"]) < TOL
 
 
-@pytest.mark.parametrize("dim", [2, 4, 5])
+@pytest.mark.parametrize("dim", [2, 3, 4, 5, 6])
 def test_timebin(golden_dir, dim):
     z = load(golden_dir, f"fortran_timebin_d{dim}.npz")
     args = (F(z["dm_1"]), F(z["dm_2"]), z["rho_init"], z["t1"], F(z["precalc"]), float(z["dt"]), dim)
