@@ -175,10 +175,33 @@ int pqd_dressed_timing(pqd_ctx* ctx, double* ms_kernel);
  * Liouvillian whose norm bound times a sub-step stays below 4096 (PQD_PATH_HILBERT); with a PT of pqd_pt_create_wide
  * dim in [2, 24] equal to the PT's, at most 8 jump operators and the same norm bound at every dim, chi <= 256
  * (PQD_PATH_HILBERT_PT; its workspace of n_traj chi dim^2 16 bytes: PQD_ERR_NOMEM when it cannot be allocated);
- * n_chan <= 4. pqd_pt_create, pqd_free_propagators, pqd_dressed_states and the map-chain calls keep dim <= 6. */
+ * n_chan <= 4. pqd_pt_create, pqd_free_propagators, pqd_dressed_states and the map-chain calls keep dim <= 6.
+ * Dynamical maps at dim in [2, 24] come from pqd_dynmap_wide (below), which runs the same two paths. */
 int pqd_propagate(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* grid, const pqd_pt* pt,
                   const int32_t* sched, const pqd_c128* rho0, int32_t n_out, const pqd_c128* out_ops,
                   const pqd_traj* traj, pqd_c128* out, int64_t out_len);
+
+/* Dynamical maps on the Hilbert-space paths, dim in [2, 24]: dm[m][n][alpha][beta] (row-major, n_maps x n_steps x
+ * N^2 x N^2, acting on row-major vec(rho)) = element alpha of the state that started as the basis element beta
+ * (|i><j|, beta = i N + j) at ta[m], after step n + 1 of grid->n_steps steps of grid->dt: the map E(ta[m] + (n + 1) dt,
+ * ta[m]). ta NULL: every map starts at grid->ta. The n_mto MTOs (pqd_traj's step, before, kind and operator arrays,
+ * without a trajectory index) are applied inside every map, in the order of a step. pt NULL (PQD_PATH_HILBERT's
+ * arithmetic) or a pqd_pt_create_wide handle (PQD_PATH_HILBERT_PT's: the closed reduced state is read out). One launch
+ * of n_maps N^2 workgroups; the maps are assembled on the device and downloaded once.
+ * PQD_ERR_ARG: n_maps < 1, n_steps < 1, dm_len != n_maps n_steps N^4, bad MTO arrays, a PT of pqd_pt_create.
+ * PQD_ERR_UNSUPPORTED: dim outside [2, 24], more than 8 jump operators, more than 4 channels, a norm bound times a
+ * sub-step above 4096, n_maps N^2 workgroups above the grid limit. PQD_ERR_NOMEM: the device buffers (twice
+ * n_maps n_steps N^4 16 bytes, with a PT the workspace of n_maps N^2 chi N^2 16 bytes) cannot be allocated.
+ * PQD_ERR_NUMERIC (maps still copied): a non-finite value. pqd_dynmap_timing: duration (ms, HIP events) of the
+ * propagation kernel of the context's last pqd_dynmap_wide call. */
+int pqd_dynmap_wide(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* grid,
+                    const pqd_pt* pt /* NULL or a pqd_pt_create_wide handle */,
+                    const int32_t* sched,
+                    int32_t n_maps, const double* ta /* n_maps start times; NULL: grid->ta */,
+                    int32_t n_mto, const int32_t* mto_step, const int32_t* mto_before,
+                    const int32_t* mto_kind, const pqd_c128* mto_ops,
+                    pqd_c128* dm, int64_t dm_len /* n_maps*n_steps*N^4 */);
+int pqd_dynmap_timing(pqd_ctx* ctx, double* ms_kernel);
 
 /* multi-system batch (pulse / field parameter scans): n_sys systems of equal dim share
  * grid, PT, initial state and output operators; trajectory t uses systems[traj_sys[t]]. This replaces the

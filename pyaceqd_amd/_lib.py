@@ -90,6 +90,9 @@ _SIGS = {
                        C.c_int32, P_C128, C.POINTER(pqd_traj), P_C128, C.c_int64], C.c_int),
     "pqd_propagate_multi": ([C.c_void_p, C.c_int32, C.POINTER(pqd_system), P_I32, C.POINTER(pqd_grid), C.c_void_p,
                              P_I32, P_C128, C.c_int32, P_C128, C.POINTER(pqd_traj), P_C128, C.c_int64], C.c_int),
+    "pqd_dynmap_wide": ([C.c_void_p, C.POINTER(pqd_system), C.POINTER(pqd_grid), C.c_void_p, P_I32, C.c_int32, P_F64,
+                         C.c_int32, P_I32, P_I32, P_I32, P_C128, P_C128, C.c_int64], C.c_int),
+    "pqd_dynmap_timing": ([C.c_void_p, P_F64], C.c_int),
     "pqd_propagate_table": ([C.c_void_p, C.c_int32, C.POINTER(pqd_system), P_I32, C.POINTER(pqd_grid), C.c_void_p,
                              P_I32, P_C128, C.c_int32, P_C128, C.POINTER(pqd_traj), P_C128, C.c_int64], C.c_int),
     "pqd_propagate_trapz": ([C.c_void_p, C.c_int32, C.POINTER(pqd_system), P_I32, C.POINTER(pqd_grid), C.c_void_p,

@@ -32,6 +32,11 @@
 // LDS (dynamic, 16-byte elements): R (rho, and the running sum), T, Tn (Taylor terms), K(t), Kd = K(t)^dag (so that both
 // products read consecutive addresses across lanes), B_0 .. B_{nl-1}; then the nonzero lists. At N = 24 with 8 jump
 // operators: 13 * 9216 B + 32 KiB = 149 KiB.
+//
+// Map instances (template parameter MAP, launch_hilbert_map): n_maps * N^2 trajectories of one system,
+// trajectory m N^2 + beta from the basis element beta at the map's own start time, the state itself stored after every
+// step in place of the output sums. A dynamical map is these columns (map_assemble_kernel, pqd_util.hip). The
+// instances with MAP = false are the kernel as it was.
 #include "pqd_common.h"
 
 namespace {
@@ -61,13 +66,15 @@ __device__ __forceinline__ double2 hb_dense(const double2* __restrict__ A, const
     return acc;
 }
 
-template <bool CSR_LDS>
+// MAP: the map instance (HilbertParams, map mode): the trajectory starts from a basis element at its map's own time
+// and stores its state after every step in place of the output sums. Everything else of a step is the same code.
+template <bool CSR_LDS, bool MAP>
 __global__ __launch_bounds__(HB_NT_MAX) void lind_hilbert_kernel(HilbertParams p) {
     extern __shared__ __attribute__((aligned(16))) char hb_smem[];
     const int tid = threadIdx.x, nt = blockDim.x;
     const int t = blockIdx.x;
     const int N = p.N, NN = N * N;
-    const HilbertSys sy = p.systems[p.traj_sys[t]];
+    const HilbertSys sy = p.systems[MAP ? 0 : p.traj_sys[t]];
     const int nl = sy.n_lind < HB_LMAX ? sy.n_lind : HB_LMAX;
     const int nc = sy.n_chan < 4 ? sy.n_chan : 4;
     // the thread's element; threads past the matrix (the last wave's tail) only take part in barriers, copies and
@@ -96,7 +103,11 @@ __global__ __launch_bounds__(HB_NT_MAX) void lind_hilbert_kernel(HilbertParams p
         for (int z = tid; z < nl * (N + 1); z += nt) lr[z] = sy.rowptr[z];
         nzv = lv; nzg = lg; nzc = lc; nzr = lr;
     }
-    if (own) R[e] = p.rho0[e];
+    if constexpr (MAP) {
+        if (own) R[e] = e == t % NN ? make_double2(1.0, 0.0) : c_zero();
+    } else {
+        if (own) R[e] = p.rho0[e];
+    }
     __syncthreads();
     // the thread's rows of every jump operator's list: row i (pass 1), row j (pass 2)
     int ib[HB_LMAX], ie[HB_LMAX], jb[HB_LMAX], je[HB_LMAX];
@@ -109,10 +120,11 @@ __global__ __launch_bounds__(HB_NT_MAX) void lind_hilbert_kernel(HilbertParams p
         }
     }
 
-    const int wb = p.wbeg[t], we = p.wend[t];
-    const long long wo = p.woff[t];
-    int ev_cur = p.ev_start[t];
-    const int ev_lim = p.ev_start[t + 1];
+    const int wb = MAP ? 0 : p.wbeg[t], we = MAP ? p.map_steps : p.wend[t];
+    const long long wo = MAP ? (long long)t * p.map_steps * NN : p.woff[t];
+    int ev_cur = MAP ? 0 : p.ev_start[t];
+    const int ev_lim = MAP ? p.map_nev : p.ev_start[t + 1];
+    const double ta = MAP ? p.map_ta[t / NN] : p.ta;
     const int nsub = p.n_sub > 0 ? p.n_sub : 1;
     const double w = 0.5 * p.dt / nsub;
     const int lane = tid & 63, wave = tid >> 6, n_waves = nt >> 6;
@@ -139,7 +151,10 @@ __global__ __launch_bounds__(HB_NT_MAX) void lind_hilbert_kernel(HilbertParams p
 
     apply_mtos(0, 0);
     for (int n = 0;; ++n) {
-        if (wb <= n && n <= we) {
+        if constexpr (MAP) {
+            // the state itself, every thread its own element (which it wrote last): no barrier
+            if (n >= 1 && own) p.out[wo + (long long)(n - 1) * NN + e] = R[e];
+        } else if (wb <= n && n <= we) {
             // wave v sums outputs v, v + n_waves, ...: lanes over the elements, then a butterfly (the same order in
             // every run)
             for (int k = wave; k < p.n_out; k += n_waves) {
@@ -156,7 +171,7 @@ __global__ __launch_bounds__(HB_NT_MAX) void lind_hilbert_kernel(HilbertParams p
         apply_mtos(n, 1);
         for (int h = 0; h < 2; ++h) {
             for (int js = 0; js < nsub; ++js) {
-                const double tm = p.ta + n * p.dt + h * 0.5 * p.dt + (js + 0.5) * w;
+                const double tm = ta + n * p.dt + h * 0.5 * p.dt + (js + 0.5) * w;
                 double2 f[4];
                 double nk = sy.nK0;
 #pragma unroll
@@ -243,19 +258,19 @@ __global__ __launch_bounds__(HB_NT_MAX) void lind_hilbert_kernel(HilbertParams p
     }
 }
 
-template <bool CSR_LDS>
+template <bool CSR_LDS, bool MAP>
 hipError_t hb_launch(int n_traj, const HilbertParams& p, size_t lds, hipStream_t s) {
     static unsigned attr = 0;  // per-device bitmask (the attribute belongs to the device's copy of the kernel)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
     if (dev >= 32 || !(attr & (1u << dev))) {
-        hipError_t e = hipFuncSetAttribute((const void*)lind_hilbert_kernel<CSR_LDS>,
+        hipError_t e = hipFuncSetAttribute((const void*)lind_hilbert_kernel<CSR_LDS, MAP>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)HB_LDS_MAX);
         if (e != hipSuccess) return e;
         if (dev < 32) attr |= 1u << dev;
     }
     const int nt = (p.N * p.N + 63) / 64 * 64;  // one thread per element, whole waves
-    hipLaunchKernelGGL(lind_hilbert_kernel<CSR_LDS>, dim3(n_traj), dim3(nt), lds, s, p);
+    hipLaunchKernelGGL((lind_hilbert_kernel<CSR_LDS, MAP>), dim3(n_traj), dim3(nt), lds, s, p);
     return hipGetLastError();
 }
 
@@ -268,6 +283,16 @@ hipError_t launch_hilbert(int n_traj, const HilbertParams& p, hipStream_t s) {
     if (p.N < 2 || p.N > HB_NMAX || p.nl_max < 0 || p.nl_max > HB_LMAX || p.csr_lds < 0 || p.csr_lds > HB_CSR_LDS)
         return hipErrorInvalidValue;
     const size_t mats = (size_t)(5 + p.nl_max) * p.N * p.N * sizeof(double2);
-    if (p.csr_lds) return hb_launch<true>(n_traj, p, mats + p.csr_lds, s);
-    return hb_launch<false>(n_traj, p, mats, s);
+    if (p.csr_lds) return hb_launch<true, false>(n_traj, p, mats + p.csr_lds, s);
+    return hb_launch<false, false>(n_traj, p, mats, s);
+}
+
+hipError_t launch_hilbert_map(int n_traj, const HilbertParams& p, hipStream_t s) {
+    if (n_traj <= 0) return hipSuccess;
+    if (p.N < 2 || p.N > HB_NMAX || p.nl_max < 0 || p.nl_max > HB_LMAX || p.csr_lds < 0 || p.csr_lds > HB_CSR_LDS)
+        return hipErrorInvalidValue;
+    if (n_traj % (p.N * p.N) || !p.map_ta || p.map_steps < 1 || p.map_nev < 0 || !p.out) return hipErrorInvalidValue;
+    const size_t mats = (size_t)(5 + p.nl_max) * p.N * p.N * sizeof(double2);
+    if (p.csr_lds) return hb_launch<true, true>(n_traj, p, mats + p.csr_lds, s);
+    return hb_launch<false, true>(n_traj, p, mats, s);
 }

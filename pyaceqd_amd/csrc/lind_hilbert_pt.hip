@@ -9,7 +9,7 @@
 // waves hand values over through __syncthreads().
 //
 // Free half step: the n_sub exponential-midpoint factors of lind_hilbert.hip, with its midpoints, channel samples,
-// norm bound, s and deg (restated here, lind_hilbert.hip is untouched). K(t), K(t)^dag, s and deg depend on the system
+// norm bound, s and deg (restated here). K(t), K(t)^dag, s and deg depend on the system
 // and the time only: they are built once per sub-step and shared by all slices. The slices are independent: G of them
 // are in flight at a time, each group of threads with its own R, T, Tn and B_k in LDS (thread lt of a group owns
 // element lt of its slice's matrices, the groups are whole waves). A group loads its slice from the workspace, takes it
@@ -53,7 +53,9 @@ __device__ __forceinline__ double2 hp_dense(const double2* __restrict__ A, const
     return acc;
 }
 
-template <bool CSR_LDS>
+// MAP: the map instance (HilbertParams, map mode): rho0 is a basis element, the start time the map's own, and the closed
+// reduced state is stored after every step in place of the output sums.
+template <bool CSR_LDS, bool MAP>
 __global__ __launch_bounds__(HBPT_NT_MAX) void lind_hilbert_pt_kernel(HilbertPtParams q) {
     extern __shared__ __attribute__((aligned(16))) char hp_smem[];
     const HilbertParams& p = q.h;
@@ -62,7 +64,7 @@ __global__ __launch_bounds__(HBPT_NT_MAX) void lind_hilbert_pt_kernel(HilbertPtP
     const int N = p.N, NN = N * N;
     const int chi = q.chi, G = q.G;
     const int nt1 = nt / G;  // threads of a group: N^2 rounded up to whole waves
-    const HilbertSys sy = p.systems[p.traj_sys[t]];
+    const HilbertSys sy = p.systems[MAP ? 0 : p.traj_sys[t]];
     const int nl = sy.n_lind < HB_LMAX ? sy.n_lind : HB_LMAX;
     const int nc = sy.n_chan < 4 ? sy.n_chan : 4;
     const int gi = tid / nt1, lt = tid - gi * nt1;
@@ -95,7 +97,8 @@ __global__ __launch_bounds__(HBPT_NT_MAX) void lind_hilbert_pt_kernel(HilbertPtP
     // initial state rho0 (x) bond0
     for (int z = tid; z < chi * NN; z += nt) {
         const int d = z / NN;
-        X[z] = c_mul(p.rho0[z - d * NN], q.bond0[d]);
+        if constexpr (MAP) X[z] = z - d * NN == t % NN ? q.bond0[d] : c_zero();
+        else X[z] = c_mul(p.rho0[z - d * NN], q.bond0[d]);
     }
     __syncthreads();
     int ib[HB_LMAX], ie[HB_LMAX], jb[HB_LMAX], je[HB_LMAX];
@@ -108,10 +111,11 @@ __global__ __launch_bounds__(HBPT_NT_MAX) void lind_hilbert_pt_kernel(HilbertPtP
         }
     }
 
-    const int wb = p.wbeg[t], we = p.wend[t];
-    const long long wo = p.woff[t];
-    int ev_cur = p.ev_start[t];
-    const int ev_lim = p.ev_start[t + 1];
+    const int wb = MAP ? 0 : p.wbeg[t], we = MAP ? p.map_steps : p.wend[t];
+    const long long wo = MAP ? (long long)t * p.map_steps * NN : p.woff[t];
+    int ev_cur = MAP ? 0 : p.ev_start[t];
+    const int ev_lim = MAP ? p.map_nev : p.ev_start[t + 1];
+    const double ta = MAP ? p.map_ta[t / NN] : p.ta;
     const int nsub = p.n_sub > 0 ? p.n_sub : 1;
     const double w = 0.5 * p.dt / nsub;
     const int lane = tid & 63, wave = tid >> 6, n_waves = nt >> 6;
@@ -144,7 +148,19 @@ __global__ __launch_bounds__(HBPT_NT_MAX) void lind_hilbert_pt_kernel(HilbertPtP
 
     apply_mtos(0, 0);
     for (int n = 0;; ++n) {
-        if (wb <= n && n <= we) {
+        if constexpr (MAP) {
+            if (n >= 1) {
+                // rho_red = sum_d c[d] X[d], d ascending, straight to the map's staging buffer
+                const double2* cl = q.closure + (size_t)q.sched[n - 1] * chi;
+                __syncthreads();  // half step b left the slices in the workspace, each stored by its own group
+                for (int a = tid; a < NN; a += nt) {
+                    double2 r = c_zero();
+                    for (int d = 0; d < chi; ++d) c_fma(r, cl[d], X[(size_t)d * NN + a]);
+                    p.out[wo + (long long)(n - 1) * NN + a] = r;
+                }
+                __syncthreads();  // the workspace is read above and written below
+            }
+        } else if (wb <= n && n <= we) {
             // rho_red = sum_d c[d] X[d], d ascending, into LDS (over K: the next sub-step rebuilds it)
             const double2* cl = n == 0 ? q.closure0 : q.closure + (size_t)q.sched[n - 1] * chi;
             __syncthreads();  // half step b left the slices in the workspace, each stored by its own group
@@ -170,7 +186,7 @@ __global__ __launch_bounds__(HBPT_NT_MAX) void lind_hilbert_pt_kernel(HilbertPtP
         apply_mtos(n, 1);
         for (int h = 0; h < 2; ++h) {
             for (int js = 0; js < nsub; ++js) {
-                const double tm = p.ta + n * p.dt + h * 0.5 * p.dt + (js + 0.5) * w;
+                const double tm = ta + n * p.dt + h * 0.5 * p.dt + (js + 0.5) * w;
                 double2 f[4];
                 double nk = sy.nK0;
 #pragma unroll
@@ -298,24 +314,23 @@ __global__ __launch_bounds__(HBPT_NT_MAX) void lind_hilbert_pt_kernel(HilbertPtP
     }
 }
 
-template <bool CSR_LDS>
+template <bool CSR_LDS, bool MAP>
 hipError_t hp_launch(int n_traj, const HilbertPtParams& q, int nt, size_t lds, hipStream_t s) {
     static size_t attr[32] = {};  // per device: the dynamic LDS the device's copy of the kernel is allowed so far
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
     if (dev >= 32 || lds > attr[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)lind_hilbert_pt_kernel<CSR_LDS>,
+        hipError_t e = hipFuncSetAttribute((const void*)lind_hilbert_pt_kernel<CSR_LDS, MAP>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         if (dev < 32) attr[dev] = lds;
     }
-    hipLaunchKernelGGL(lind_hilbert_pt_kernel<CSR_LDS>, dim3(n_traj), dim3(nt), lds, s, q);
+    hipLaunchKernelGGL((lind_hilbert_pt_kernel<CSR_LDS, MAP>), dim3(n_traj), dim3(nt), lds, s, q);
     return hipGetLastError();
 }
 
-}  // namespace
-
-hipError_t launch_hilbert_pt(int n_traj, const HilbertPtParams& q, hipStream_t s) {
+template <bool MAP>
+hipError_t hp_checked_launch(int n_traj, const HilbertPtParams& q, hipStream_t s) {
     if (n_traj <= 0) return hipSuccess;
     const HilbertParams& p = q.h;
     if (p.N < 2 || p.N > HB_NMAX || p.nl_max < 0 || p.nl_max > HB_LMAX || p.csr_lds < 0 || p.csr_lds > HB_CSR_LDS)
@@ -329,6 +344,19 @@ hipError_t launch_hilbert_pt(int n_traj, const HilbertPtParams& q, hipStream_t s
         return hipErrorInvalidValue;
     const size_t lds = (size_t)q.lds_elems * sizeof(double2) + p.csr_lds;
     if (lds > (size_t)HBPT_LDS_MAX) return hipErrorInvalidValue;
-    if (p.csr_lds) return hp_launch<true>(n_traj, q, q.G * nt1, lds, s);
-    return hp_launch<false>(n_traj, q, q.G * nt1, lds, s);
+    if (p.csr_lds) return hp_launch<true, MAP>(n_traj, q, q.G * nt1, lds, s);
+    return hp_launch<false, MAP>(n_traj, q, q.G * nt1, lds, s);
+}
+
+}  // namespace
+
+hipError_t launch_hilbert_pt(int n_traj, const HilbertPtParams& q, hipStream_t s) {
+    return hp_checked_launch<false>(n_traj, q, s);
+}
+
+hipError_t launch_hilbert_pt_map(int n_traj, const HilbertPtParams& q, hipStream_t s) {
+    const HilbertParams& p = q.h;
+    if (n_traj > 0 && (p.N < 2 || n_traj % (p.N * p.N) || !p.map_ta || p.map_steps < 1 || p.map_nev < 0 || !p.out))
+        return hipErrorInvalidValue;
+    return hp_checked_launch<true>(n_traj, q, s);
 }

@@ -350,9 +350,20 @@ struct HilbertParams {
     double2* out;
     int csr_lds;             // > 0: bytes of LDS for the nonzero lists (the largest system's, hilbert_csr_bytes), read
                              //   from LDS; 0: a system's lists exceed HB_CSR_LDS, all are read from global memory
+    // map mode only (the MAP instances; launch_hilbert_map, launch_hilbert_pt_map): n_maps * N^2 trajectories of
+    // systems[0]. Trajectory m N^2 + beta starts from the basis element beta (|i><j|, beta = i N + j) at map_ta[m],
+    // runs map_steps steps with the events [0, map_nev) of ev, and stores its state (with a PT: the closed reduced
+    // state) after every step n >= 1 to out[(trajectory * map_steps + n - 1) * N^2 + element]. rho0, ovec, n_out,
+    // ta, traj_sys, wbeg, wend, woff and ev_start are not read
+    const double* map_ta;    // n_maps start times
+    int map_steps, map_nev;
 };
 size_t hilbert_csr_bytes(int N, int n_lind, int nnz);  // LDS bytes of one system's nonzero lists (a multiple of 16)
 hipError_t launch_hilbert(int n_traj, const HilbertParams& p, hipStream_t s);
+hipError_t launch_hilbert_map(int n_traj, const HilbertParams& p, hipStream_t s);  // n_traj = n_maps * N^2
+// dm[m][n][alpha][beta] = stage[((m N^2 + beta) n_steps + n) N^2 + alpha]: the states the map instances stored, as
+// n_maps * n_steps row-major N^2 x N^2 maps (pqd_util.hip: 32 x 32 tiles through LDS, reads and writes coalesced)
+hipError_t launch_map_assemble(const double2* stage, double2* dm, int N2, int n_maps, int n_steps, hipStream_t s);
 
 // Hilbert-space propagation with a process tensor (lind_hilbert_pt.hip): the state rho (x) bond as chi slices of N x N
 // in a per-plan workspace, the free half steps of lind_hilbert.hip on G slices at a time, the PT slice per element
@@ -378,6 +389,7 @@ struct HilbertPtParams {
 constexpr size_t hbpt_mat_elems(int N, int nl_max, int G) { return (size_t)(2 + G * (3 + nl_max)) * N * N; }
 constexpr size_t hbpt_unit_elems(int chi) { return (size_t)HBPT_EB * (chi | 1); }
 hipError_t launch_hilbert_pt(int n_traj, const HilbertPtParams& p, hipStream_t s);
+hipError_t launch_hilbert_pt_map(int n_traj, const HilbertPtParams& p, hipStream_t s);  // map mode (HilbertParams)
 
 // launchers (defined in the .hip translation units)
 hipError_t launch_dressed(int N, const DressedParams& p, hipStream_t s);       // N = 2..6 (dressed.hip)

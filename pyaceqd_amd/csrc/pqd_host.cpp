@@ -186,6 +186,7 @@ struct pqd_ctx {
     // map-chain sweeps: one device arena reused across calls (grown on demand), so a call allocates nothing
     DevBuf<char> mc_arena;
     double dressed_ms = -1.0;  // kernel duration of the last pqd_dressed_states call (pqd_dressed_timing)
+    double dynmap_ms = -1.0;   // duration of the map instance of the last pqd_dynmap_wide call (pqd_dynmap_timing)
 };
 
 namespace {
@@ -2176,6 +2177,117 @@ int pqd_propagate_table(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems, 
     if (!rc) rc = pqd_plan_download_table(P, table, table_len);
     pqd_plan_destroy(P);
     return rc;
+}
+
+// Dynamical maps on the Hilbert-space path: n_maps * N^2 trajectories of one system in one launch of a map instance
+// (lind_hilbert.hip, lind_hilbert_pt.hip), trajectory m N^2 + beta from the basis element beta at ta[m], every one
+// with the caller's MTOs; then the assembly into dm[m][n][alpha][beta] on the device (pqd_util.hip), the finite check
+// and one download. The system tables, the events and (with a PT) the units, G and the tile are those a plan of one
+// trajectory with these MTOs gets (setup_hilbert, setup_hilbert_pt); only the bond workspace is sized for all.
+int pqd_dynmap_wide(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* grid, const pqd_pt* pt, const int32_t* sched,
+                    int32_t n_maps, const double* ta, int32_t n_mto, const int32_t* mto_step,
+                    const int32_t* mto_before, const int32_t* mto_kind, const pqd_c128* mto_ops, pqd_c128* dm,
+                    int64_t dm_len) {
+    if (!ctx) return fail(PQD_ERR_ARG, "ctx is NULL");
+    int rc = check_system(sys, HB_NMAX);
+    if (rc) return rc;
+    if ((rc = check_grid(grid))) return rc;
+    const int N = sys->dim, NN = N * N, ns = grid->n_steps;
+    if (sys->n_lind > HB_LMAX)
+        return fail(PQD_ERR_UNSUPPORTED, "n_lind %d not in [0, %d] on the Hilbert-space path", sys->n_lind, HB_LMAX);
+    if (n_maps < 1) return fail(PQD_ERR_ARG, "n_maps %d must be >= 1", n_maps);
+    if (ns < 1) return fail(PQD_ERR_ARG, "n_steps %d must be >= 1", ns);
+    const int64_t n_traj = (int64_t)n_maps * NN;
+    if (n_traj > INT_MAX)
+        return fail(PQD_ERR_UNSUPPORTED, "n_maps %d x dim^2 %d = %lld workgroups exceed the grid limit %d", n_maps, NN,
+                    (long long)n_traj, INT_MAX);
+    const int64_t need = (int64_t)n_maps * ns * NN * NN;
+    if (dm_len != need)
+        return fail(PQD_ERR_ARG, "dm_len %lld != n_maps * n_steps * dim^4 = %lld", (long long)dm_len, (long long)need);
+    if (!dm) return fail(PQD_ERR_ARG, "dm is NULL");
+    if (n_mto < 0 || (n_mto > 0 && (!mto_step || !mto_before || !mto_kind || !mto_ops)))
+        return fail(PQD_ERR_ARG, "bad MTO arrays");
+    for (int q = 0; q < n_mto; ++q) {
+        if (mto_step[q] < 0 || mto_step[q] > ns) return fail(PQD_ERR_ARG, "MTO %d: step %d outside [0, %d]", q, mto_step[q], ns);
+        if (mto_kind[q] < 0 || mto_kind[q] > 2) return fail(PQD_ERR_ARG, "MTO %d: kind %d", q, mto_kind[q]);
+    }
+    std::vector<int32_t> sch(ns, 0);
+    if (pt) {
+        if (pt->ctx != ctx) return fail(PQD_ERR_ARG, "PT belongs to another context");
+        if (!pt->wide) return fail(PQD_ERR_ARG, "the PT handle is not one of pqd_pt_create_wide");
+        if (pt->dim != N) return fail(PQD_ERR_ARG, "PT dim %d != system dim %d", pt->dim, N);
+        for (int n = 0; n < ns; ++n) {
+            const int v = sched ? sched[n] : std::min(n, pt->n_slices - 1);
+            if (v < 0 || v >= pt->n_slices) return fail(PQD_ERR_ARG, "sched[%d]=%d out of [0,%d)", n, v, pt->n_slices);
+            sch[n] = v;
+        }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const PlanEnv env = read_plan_env();
+
+    // the plan of one template trajectory: system table, norm-bound refusal, events in the order of a step
+    pqd_plan P;
+    P.ctx = ctx; P.N2 = NN; P.n_traj = 1; P.n_steps = ns; P.n_sys = 1; P.n_out = 0; P.out_len = 0;
+    const int32_t w0 = 0, w1 = ns;
+    const int64_t o0 = 0;
+    const std::vector<int32_t> mtraj(std::max(1, (int)n_mto), 0);
+    const pqd_traj tr{1, &w0, &w1, &o0, n_mto, mtraj.data(), mto_step, mto_before, mto_kind, mto_ops};
+    const std::vector<int> tsys(1, 0);
+    const std::vector<cd> zero(NN, 0.0);  // rho0 of the template: the map instances start from basis elements
+    if ((rc = setup_hilbert(&P, sys, tsys, grid, reinterpret_cast<const pqd_c128*>(zero.data()), nullptr, &tr, s))) return rc;
+    P.n_traj = (int)n_traj;  // sizes the bond workspace
+    if (pt && (rc = setup_hilbert_pt(&P, pt, sch, env, s))) return rc;
+
+    std::vector<double> tav(n_maps);
+    for (int m = 0; m < n_maps; ++m) tav[m] = ta ? ta[m] : grid->ta;
+    DevBuf<double> ta_d;
+    DevBuf<double2> stage, dmd;
+    HIPCHK(ta_d.upload(tav.data(), tav.size(), s));
+    hipError_t e = stage.alloc((size_t)need);
+    if (e == hipSuccess) e = dmd.alloc((size_t)need);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? PQD_ERR_NOMEM : PQD_ERR_HIP, "map buffers of 2 x %lld bytes: %s",
+                    (long long)need * (long long)sizeof(double2), hipGetErrorString(e));
+    HilbertParams& hp = pt ? P.hq.h : P.hp;
+    hp.map_ta = ta_d.p; hp.map_steps = ns; hp.map_nev = n_mto; hp.out = stage.p;
+
+    hipEvent_t ev[2];
+    HIPCHK(hipEventCreate(&ev[0]));
+    if (hipError_t e1 = hipEventCreate(&ev[1]); e1 != hipSuccess) {
+        (void)hipEventDestroy(ev[0]);
+        return fail(PQD_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e1));
+    }
+    auto run = [&]() -> int {
+        HIPCHK(hipEventRecord(ev[0], s));
+        if (pt) HIPCHK(launch_hilbert_pt_map((int)n_traj, P.hq, s));
+        else HIPCHK(launch_hilbert_map((int)n_traj, P.hp, s));
+        HIPCHK(hipEventRecord(ev[1], s));
+        HIPCHK(launch_map_assemble(stage.p, dmd.p, NN, n_maps, ns, s));
+        unsigned flags = 0;
+        HIPCHK(launch_check_finite(dmd.p, need, P.flags.p, s));
+        HIPCHK(hipMemcpyAsync(&flags, P.flags.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        touch_pages(dm, (size_t)need * sizeof(double2));
+        HIPCHK(hipMemcpyAsync(dm, dmd.p, (size_t)need * sizeof(double2), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        ctx->dynmap_ms = ms;
+        // the values are handed over all the same (they show where the run went bad)
+        if (flags & 1u) return fail(PQD_ERR_NUMERIC, "non-finite value (NaN/Inf) in the dynamical maps");
+        return PQD_OK;
+    };
+    rc = run();
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    return rc;
+}
+
+int pqd_dynmap_timing(pqd_ctx* ctx, double* ms_kernel) {
+    if (!ctx || !ms_kernel) return fail(PQD_ERR_ARG, "NULL argument");
+    if (ctx->dynmap_ms < 0) return fail(PQD_ERR_ARG, "no pqd_dynmap_wide call has completed on this context");
+    *ms_kernel = ctx->dynmap_ms;
+    return PQD_OK;
 }
 
 int pqd_fail_msg(int code, const char* msg) { return fail(code, "%s", msg); }

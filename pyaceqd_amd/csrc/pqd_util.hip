@@ -63,7 +63,44 @@ __global__ __launch_bounds__(256) void trapz_kernel(const double2* __restrict__ 
     }
 }
 
+// The states the map instances of the Hilbert-space kernels stored (trajectory m N2 + beta, step n, element alpha;
+// pqd_common.h HilbertParams) as the maps dm[m][n][alpha][beta]: an N2 x N2 transpose per (m, n) whose source rows
+// lie n_steps N2 elements apart. 32 x 32 tiles through LDS (row stride 33: both accesses conflict-free), 256
+// threads as 32 x 8; reads run along alpha, writes along beta. Workgroups stride over the tiles (64-bit count).
+__global__ __launch_bounds__(256) void map_assemble_kernel(const double2* __restrict__ stage, double2* __restrict__ dm,
+                                                           int N2, int n_maps, int n_steps) {
+    __shared__ double2 tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int nt = (N2 + 31) / 32;
+    const long long items = (long long)n_maps * n_steps * nt * nt;
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int tb = (int)(it % nt), ta = (int)(it / nt % nt);
+        const long long mn = it / ((long long)nt * nt);
+        const long long m = mn / n_steps, n = mn - m * n_steps;
+#pragma unroll
+        for (int k = 0; k < 32; k += 8) {
+            const int beta = tb * 32 + ty + k, alpha = ta * 32 + tx;
+            if (beta < N2 && alpha < N2) tile[ty + k][tx] = stage[((m * N2 + beta) * n_steps + n) * N2 + alpha];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 32; k += 8) {
+            const int alpha = ta * 32 + ty + k, beta = tb * 32 + tx;
+            if (alpha < N2 && beta < N2) dm[(mn * N2 + alpha) * N2 + beta] = tile[tx][ty + k];
+        }
+        __syncthreads();  // the tile is read above and overwritten by the next item
+    }
+}
+
 }  // namespace
+
+hipError_t launch_map_assemble(const double2* stage, double2* dm, int N2, int n_maps, int n_steps, hipStream_t s) {
+    if (N2 < 1 || n_maps < 1 || n_steps < 1 || !stage || !dm) return hipErrorInvalidValue;
+    const long long nt = (N2 + 31) / 32, items = (long long)n_maps * n_steps * nt * nt;
+    hipLaunchKernelGGL(map_assemble_kernel, dim3((unsigned)std::min<long long>(items, 1 << 20)), dim3(256), 0, s, stage,
+                       dm, N2, n_maps, n_steps);
+    return hipGetLastError();
+}
 
 hipError_t launch_trapz(const double2* out, const long long* woff, const int* wbeg, const int* wend, int n_traj,
                         int n_out, int n_pairs, const int* kh, const int* kt, double dx, double2* res, hipStream_t s) {

@@ -345,6 +345,53 @@ def free_propagators(system: System, grid: Grid, ctx=None):
     return M[: 2 * grid.n_steps]
 
 
+def dynmap_wide(system: System, grid: Grid, pt: Optional[ProcessTensor] = None, mtos: Sequence = (), ta=None,
+                ctx=None):
+    """Dynamical maps on the Hilbert-space paths (pqd_dynmap_wide), dim 2..24: complex (n_maps, n_steps, N^2, N^2),
+    dm[m, n] = E(ta[m] + (n + 1) dt, ta[m]) acting on row-major vec(rho). Column beta is the state that started as the
+    basis element |i><j| (beta = i N + j), written out after every step by one workgroup; the maps are assembled on the
+    device and downloaded once. ta: the maps' start times (None: one map from grid.ta). mtos (MTO objects, `traj`
+    ignored) are applied inside every map, in the order of a step. pt: propagated as a wide handle
+    (pqd_pt_create_wide), the closed reduced state is read out. kernel time: dynmap_kernel_ms."""
+    ctx = ctx or _lib.context()
+    N = system.dim
+    tav = np.ascontiguousarray([grid.ta] if ta is None else np.atleast_1d(ta), dtype=np.float64)
+    if tav.ndim != 1 or len(tav) < 1:
+        raise ValueError("ta must be a non-empty 1-D sequence of start times")
+    mtos = list(mtos)
+    ms = mb = mk = mo = None
+    if mtos:
+        ms = np.ascontiguousarray([m.step for m in mtos], dtype=np.int32)
+        mb = np.ascontiguousarray([1 if m.before else 0 for m in mtos], dtype=np.int32)
+        mk = np.ascontiguousarray([m.kind for m in mtos], dtype=np.int32)
+        mo = _c(np.stack([np.asarray(m.op).reshape(N, N) for m in mtos]))
+    sched = None
+    if pt is not None:
+        if pt.gmap.shape[0] != N * N:
+            raise ValueError(f"PT gmap has {pt.gmap.shape[0]} entries, system needs {N * N}")
+        if pt.dt is not None and abs(float(pt.dt) - float(grid.dt)) > 1e-9 * abs(float(grid.dt)):
+            raise ValueError(f"PT was generated for dt = {pt.dt}, the grid has dt = {grid.dt}")
+        sched = pt.schedule(max(1, grid.n_steps))
+    n_steps = max(0, int(grid.n_steps))
+    dm = np.empty((len(tav), n_steps, N * N, N * N), dtype=np.complex128)
+    with ctx.lock:
+        sc, keep = system.to_c()
+        gc = grid.to_c()
+        pth = pt.handle(ctx, N, True) if pt is not None else None
+        _lib.check(_lib.lib().pqd_dynmap_wide(ctx.handle, C.byref(sc), C.byref(gc), pth, _lib.iptr(sched), len(tav),
+                                              _lib.fptr(tav), len(mtos), _lib.iptr(ms), _lib.iptr(mb), _lib.iptr(mk),
+                                              _lib.cptr(mo), _lib.cptr(dm.reshape(-1)) if dm.size else None, dm.size))
+    return dm
+
+
+def dynmap_kernel_ms(ctx=None):
+    """duration (ms, device events) of the propagation kernel of the context's last dynmap_wide call"""
+    ctx = ctx or _lib.context()
+    ms = C.c_double()
+    _lib.check(_lib.lib().pqd_dynmap_timing(ctx.handle, C.byref(ms)))
+    return ms.value
+
+
 DRESSED_LAUNCHES = 0  # pqd_dressed_states[_wide] calls issued by this process (tests count launches with it)
 
 

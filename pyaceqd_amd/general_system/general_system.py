@@ -31,6 +31,7 @@ from ..constants import hbar
 from .. import constants
 from .._lib import PQDError, PQD_ERR_UNSUPPORTED
 from .. import opgrammar
+from .. import engine as _engine  # dynmap_wide is looked up at call time
 from ..engine import Grid, MTO, ProcessTensor, System, Trajectories, free_propagators, propagate, propagate_table, \
     propagate_trapz, KIND, dressed_states, dressed_table
 
@@ -243,7 +244,7 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
                       firstonly=False, J_to_file=None, J_file=None, factor_ah=None, use_infinite=False,
                       print_H=False, calc_dynmap=False, rho0=None, get_M_t=None, trajectories=None, n_sub=1,
                       device=None, pulse_sampling="ace_file", trapz=None, dressed_rho=None, lower_only=False,
-                      wide_pt=None):
+                      wide_pt=None, wide_maps=None):
     """Propagate one trajectory (or a batch: `trajectories`) and return ACE's output table.
 
     Returns (1 + len(output_ops), n_t) complex, row 0 = time (general_system.py:104-110, 343).
@@ -277,6 +278,14 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
     dim <= 6 and the run takes the Hilbert-space path with a PT (engine.propagate(..., wide_pt=True)). None (default)
     lets the environment switch PQD_WIDE_PT=1 decide, for scripts that cannot change their call sites; False never
     opts in. Without the opt-in phonons above dim 6 are refused as before; at dim <= 6 nothing changes either way.
+
+    wide_maps=True opts in to calc_dynmap and get_M_t above dim 6 (dim <= 24), with PQD_WIDE_MAPS=1 as its environment
+    form and the same None / False rule: the maps come from engine.dynmap_wide, one workgroup per column, and `result`
+    from the ordinary propagation of the call. calc_dynmap with phonons=True needs wide_pt as well. Without the opt-in
+    both are refused as before; at dim <= 6 the switch changes nothing.
+
+    get_M_t may be a 1-D sequence of times at every dim: the result is then (len, N^2, N^2), the one-step maps
+    E(t + dt, t) without a PT (above dim 6 one launch under the opt-in, at dim <= 6 the scalar result per time).
     """
     if pulse_sampling not in ("exact", "ace_file"):
         raise ValueError(f"pulse_sampling must be 'exact' or 'ace_file', not {pulse_sampling!r}")
@@ -308,17 +317,23 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
         dim = 2  # "assuming TLS" (:19)
     mat = lambda s: opgrammar.to_matrix(s, dim)  # noqa: E731
     wide = (os.environ.get("PQD_WIDE_PT") == "1") if wide_pt is None else bool(wide_pt)
+    maps = (os.environ.get("PQD_WIDE_MAPS") == "1") if wide_maps is None else bool(wide_maps)
     if dim > 6:
         # above dim 6 the propagation runs in Hilbert space (dim <= 24): without a PT, or with one under the wide_pt
         # opt-in. Everything that builds N^2 x N^2 superoperators stops at 6. Refused here, before a PT is generated
         # or read
         from .._lib import HILBERT_MAX_DIM
         wide = wide and dim <= HILBERT_MAX_DIM
-        for name, on in (("phonons=True", phonons and not wide), ("calc_dynmap", calc_dynmap),
-                         ("get_M_t", get_M_t is not None), ("dressedstates", dressedstates)):
+        maps = maps and dim <= HILBERT_MAX_DIM
+        # get_M_t uses no PT and returns before one is resolved: phonons=True does not stand in its way
+        for name, on in (("phonons=True", phonons and not wide and not (maps and get_M_t is not None)),
+                         ("calc_dynmap", calc_dynmap and not maps),
+                         ("get_M_t", get_M_t is not None and not maps), ("dressedstates", dressedstates)):
             if on:
                 hint = "; wide_pt=True or PQD_WIDE_PT=1 propagates it with phonons" \
                     if name == "phonons=True" and dim <= HILBERT_MAX_DIM else ""
+                if name in ("calc_dynmap", "get_M_t") and dim <= HILBERT_MAX_DIM:
+                    hint = "; wide_maps=True or PQD_WIDE_MAPS=1 builds the maps in Hilbert space"
                 raise NotImplementedError(f"{name} needs dim <= 6, this system has dim {dim} (without it a system "
                                           f"of dim <= {HILBERT_MAX_DIM} propagates{hint})")
     # engine.* receive wide_pt only where it applies: a PT above dim 6 under the opt-in
@@ -463,9 +478,22 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
         return tabs if trajectories is not None else tabs[0]
 
     if get_M_t is not None:
-        g1 = Grid(get_M_t, dt, 1, n_sub)
-        M = free_propagators(system, g1)
-        return M[1] @ M[0]
+        # the one-step map(s) E(t + dt, t) of the run's system, without a PT; a 1-D sequence of times gives a stack
+        tms = np.asarray(get_M_t, dtype=float)
+        if tms.ndim > 1:
+            raise ValueError("get_M_t must be a time or a 1-D sequence of times")
+        if dim > 6:  # under the wide_maps opt-in: one launch of len * dim^2 one-step trajectories
+            from .. import _lib
+            Ms = _engine.dynmap_wide(system, Grid(t_start, dt, 1, n_sub), ta=tms.reshape(-1),
+                                     ctx=_lib.context(device))[:, 0]
+            return Ms if tms.ndim else Ms[0]
+
+        def one_step(t):
+            M = free_propagators(system, Grid(t, dt, 1, n_sub))
+            return M[1] @ M[0]
+        if tms.ndim:
+            return np.array([one_step(float(t)) for t in tms], dtype=complex).reshape(len(tms), dim * dim, dim * dim)
+        return one_step(get_M_t)
 
     # ---------------------------------------------------------------- environment
     pt = None
@@ -477,7 +505,7 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
 
     # ---------------------------------------------------------------- trajectories
     out_mats = [mat(s) for s in output_ops]
-    if calc_dynmap:
+    if calc_dynmap and dim <= 6:
         return _dynmap(system, grid, pt, rho_init, multitime_op, out_mats, t_start, dt, dim, device)
     begins, ends, mtos = [], [], []
     for k, spec in enumerate(traj_specs):
@@ -495,6 +523,15 @@ def system_ace_stream(t_start, t_end, *pulses, dt=0.01, phonons=False, t_mem=20.
     multi = len(systems) > 1
     tr = Trajectories(np.array(begins), np.array(ends), mtos, system=np.array(traj_sys) if multi else None)
     from .. import _lib
+    if calc_dynmap:
+        # dim 7..24 under the wide_maps opt-in: the maps from the map instances of the Hilbert-space kernels, with the
+        # call's MTOs inside; `result` from the ordinary propagation of rho_init
+        if trajectories is not None:
+            raise ValueError("calc_dynmap takes one trajectory (multitime_op), not `trajectories`")
+        dm = _engine.dynmap_wide(system, grid, pt=pt, mtos=mtos, ctx=_lib.context(device))[0]
+        if not n_real:
+            return grid.times[None, :].astype(complex), dm
+        return propagate_table(system, grid, rho_init, out_mats, tr, pt=pt, ctx=_lib.context(device), **wide_kw)[0], dm
     if trapz is not None:
         # (k_head, k_tail, dx): per-trajectory trapezoid integrals of output rows over the window, on the device
         # (pqd_propagate_trapz), in place of the tables: (n_traj, n_pairs) complex

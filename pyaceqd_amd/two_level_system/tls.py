@@ -8,7 +8,8 @@ radiative decay |0><1|_2, optional pure dephasing). Unknown keywords (`trajector
 Below it the reference's cavity and sensor variants (tls_one_sensor, tls_two_sensor, tls_photon, tls_photons,
 tls_photon_sensor, tls_photon_two_sensor; pyaceqd/two_level_system/tls.py:89-349), dim 4 to 24: without phonons they
 propagate at any of these sizes, everything else stops at dim 6. `phonons=True` above dim 6 is an opt-in: the forwarded
-keyword `wide_pt=True` (or PQD_WIDE_PT=1), see system_ace_stream.
+keyword `wide_pt=True` (or PQD_WIDE_PT=1), see system_ace_stream. `calc_dynmap=True` and `get_M_t` above dim 6 are an
+opt-in too: the forwarded keyword `wide_maps=True` (or PQD_WIDE_MAPS=1).
 """
 from ..general_system.general_system import system_ace_stream
 from .. import constants
@@ -16,7 +17,8 @@ from .. import constants
 hbar = constants.hbar
 temp_dir = constants.temp_dir
 
-_FWD = ("trajectories", "n_sub", "device", "pulse_sampling", "trapz", "dressed_rho", "lower_only", "wide_pt")
+_FWD = ("trajectories", "n_sub", "device", "pulse_sampling", "trapz", "dressed_rho", "lower_only", "wide_pt",
+        "wide_maps", "calc_dynmap", "get_M_t")  # the last two: for the wrappers whose signature lacks them
 
 
 def tls(t_start, t_end, *pulses, dt=0.1, gamma_e=1/100, phonons=False, t_mem=6.4, ae=5.0, temperature=4,
