@@ -221,7 +221,7 @@ int or_propagate(const or_system* sys, const or_grid* g, const or_pt* pt, const 
     for (int it = 0; it < tr->n_traj; ++it) {
         ocplx* st = malloc(sizeof(ocplx) * N2 * (size_t)chi);
         ocplx* nw = malloc(sizeof(ocplx) * N2 * (size_t)chi);
-        ocplx r[36];
+        ocplx* r = malloc(sizeof(ocplx) * N2);  /* the reduced state (any dim: the Hilbert-space kernels go to 24) */
         for (int a = 0; a < N2; ++a)
             for (int d = 0; d < chi; ++d) st[(size_t)a * chi + d] = rho0[a] * (pt ? pt->bond0[d] : 1.0);
         int nb = tr->out_begin[it], ne = tr->out_end[it];
@@ -259,7 +259,7 @@ int or_propagate(const or_system* sys, const or_grid* g, const or_pt* pt, const 
             apply_free(N2, chi, M + (size_t)(2 * n + 1) * mm2, st, nw);
             memcpy(st, nw, sizeof(ocplx) * N2 * chi);
         }
-        free(st); free(nw);
+        free(st); free(nw); free(r);
     }
     free(Mown);
     return 0;

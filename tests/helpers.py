@@ -85,6 +85,74 @@ def random_rho(N, seed=1):
     return r / np.trace(r)
 
 
+def dense_ops(N, n_out, seed):
+    """n_out full complex non-Hermitian N x N operators, normal + 1j * normal each, drawn one operator after the other:
+    dense_ops(N, m, seed) is the head of dense_ops(N, n, seed) for m < n, so cases with fewer outputs share the columns
+    of one reference"""
+    rng = np.random.default_rng(seed)
+    return [rng.normal(size=(N, N)) + 1j * rng.normal(size=(N, N)) for _ in range(n_out)]
+
+
+def dense_state(N, seed):
+    """a full complex non-Hermitian N x N matrix in place of a density matrix (the two-time callers hand over
+    operator-multiplied states)"""
+    return dense_ops(N, 1, seed)[0]
+
+
+def readout_trajectories(N, n_steps, n_traj, seed=0):
+    """Trajectories of the output-readout tests (n_steps >= 9, or 8 with up to three trajectories). Windows [b, e] are
+    ragged at both ends; trajectory 0 opens its window at step 2. Every trajectory t has three MTOs inside its window,
+    at steps b + 1, b + 2 and b + 4, of the kinds t, t + 1, t + 2 mod 3, applied before / after / after for even t and after / before / after for odd t:
+    MTOs at steps with outputs, and a single trajectory already sees the kinds 0, 1, 2 and both flags. Trajectory 0 also
+    has one at step 0 (before its window, applied before, kind 1) and a second one in its (b + 4, after) slot. The last MTO
+    is at step 7 at most, which leaves the rest of the run free of events. The operators are dense, scaled to the
+    Frobenius norm sqrt(N) of a unitary: the state keeps its size across an MTO, so every output column takes its
+    largest value from four unrelated states and no column of a 256-column table is small against the others."""
+    rng = np.random.default_rng(seed)
+
+    def op():
+        A = rng.normal(size=(N, N)) + 1j * rng.normal(size=(N, N))
+        return A * (np.sqrt(N) / np.linalg.norm(A))
+    beg = [(2, 0, 1, 3, 0)[t % 5] for t in range(n_traj)]
+    end = [n_steps - (0, 3, 1, 2, 4)[t % 5] for t in range(n_traj)]
+    mt = []
+    for t in range(n_traj):
+        b = beg[t]
+        mt += [MTO(t, b + 1, t % 2 == 0, t % 3, op()), MTO(t, b + 2, t % 2 == 1, (t + 1) % 3, op()),
+               MTO(t, b + 4, False, (t + 2) % 3, op())]
+    mt += [MTO(0, 0, True, 1, op()), MTO(0, beg[0] + 4, False, 1, op())]
+    return Trajectories(np.array(beg), np.array(end), mt)
+
+
+def readout_pt(N, chi, seed):
+    """pt.random_pt(N, chi, D=min(N * N, 9), n_slices=5, eps=0.1) of the first seed from `seed` on whose closure vectors
+    overlap the bond vector alike: |bond0 . c| within a factor 1.5 over closure0 and the five slices' closures. The
+    slices are close to the identity, so a step's outputs are those of the reduced state times that overlap, and a random
+    PT's overlaps differ up to tenfold from step to step: every column of a trajectory would take its largest value
+    at the one step with the largest overlap, and a column that happens to be small there would be small against the rest
+    of the table. With even overlaps every step of the window counts."""
+    from pyaceqd_amd import pt as ptmod
+    for s in range(seed, seed + 1000):
+        pt = ptmod.random_pt(N, chi, D=min(N * N, 9), n_slices=5, seed=s, eps=0.1)
+        w = np.abs(np.concatenate([[pt.closure0 @ pt.bond0], pt.closure @ pt.bond0]))
+        if w.max() < 1.5 * w.min():
+            return pt
+    raise AssertionError("no seed with even closure overlaps")
+
+
+def column_errors(got, ref):
+    """per trajectory and output column k: max_n |got - ref| / max_n |ref[:, k]|, as one (n_traj, n_out) array, and
+    the smallest ratio of a column's max_n |ref| to its trajectory's largest (how far the normalisation is from empty)"""
+    assert len(got) == len(ref)
+    err, ratio = [], []
+    for a, b in zip(got, ref):
+        assert a.shape == b.shape
+        cmax = np.max(np.abs(b), axis=0)
+        err.append(np.max(np.abs(a - b), axis=0) / cmax)
+        ratio.append(cmax.min() / cmax.max())
+    return np.array(err), float(min(ratio))
+
+
 def numpy_liouvillian(sysd, t):
     N = sysd.dim
     I = np.eye(N)
