@@ -286,6 +286,12 @@ int pqd_plan_sweep_lean(const pqd_plan* plan, int32_t* on);
  * steps after its last MTO and activation and before its last two steps (PQD_LEAN_RO=0 keeps the separate
  * closure pass on every step), else 0. Results agree with the other readout to rounding (the order of two sums) */
 int pqd_plan_sweep_readout(const pqd_plan* plan, int32_t* on);
+/* the number of workgroups of the plan whose fast steps (pqd_plan_sweep_readout) take the fused column operator, the
+ * output rows W(n) and the closure vector from LDS, staged there during the PT phase of the step before: every workgroup
+ * with fast steps whose trajectories all belong to one system (PQD_LEAN_STAGE=0 keeps the loads where
+ * they are used, and so do workgroups that mix systems). 0 where the plan reads no outputs in the column phase. Results
+ * are bit-identical either way */
+int pqd_plan_sweep_stage(const pqd_plan* plan, int32_t* n_blocks);
 /* every decision plan creation took, as one line of space-separated key=value pairs in a fixed order: the device's
  * CU count, path (PQD_PATH_*), workgroup shape, split / quad / multi-trajectory split / trunk layout, windows, the
  * A/B switches as the kernels will see them, and 64-bit FNV-1a hashes (hex) of the block arrays, the PT row-unit list

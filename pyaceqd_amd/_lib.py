@@ -114,6 +114,7 @@ _SIGS = {
     "pqd_plan_windows": ([C.c_void_p, P_I32], C.c_int),
     "pqd_plan_sweep_lean": ([C.c_void_p, P_I32], C.c_int),
     "pqd_plan_sweep_readout": ([C.c_void_p, P_I32], C.c_int),
+    "pqd_plan_sweep_stage": ([C.c_void_p, P_I32], C.c_int),
     "pqd_plan_describe": ([C.c_void_p, C.c_char_p, C.c_int32], C.c_int),
     "pqd_plan_info": ([C.c_void_p, P_I32, P_I32, P_I32, P_I64], C.c_int),
     "pqd_plan_timing": ([C.c_void_p, P_F64, P_F64, P_I32, C.c_int32], C.c_int),

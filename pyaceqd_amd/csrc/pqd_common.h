@@ -211,6 +211,10 @@ struct SweepParams {
                              //   each step fused, has no event left and is active (>= 1; INT_MAX: none before blk_end - 1):
                              //   from there the outputs are read inside the column phase (pt_sweep.hip LeanCol).
                              //   NULL: never (PQD_LEAN_RO=0, the trunk pre-pass, plans on the general instance)
+    const int* blk_stage;    // n_blocks, beside blk_fast: the system all occupied slots of the block share, whose F(n + 1)
+                             //   and W(n + 1) (and the closure vector step n + 1 reads) the fast region stages in LDS during
+                             //   the PT phase of step n (pt_sweep.hip LeanStage); -1: the block's slots mix systems and
+                             //   load these operands in place. NULL: no block stages (PQD_LEAN_STAGE=0, or blk_fast NULL)
 };
 
 // split groups with several trajectories per group (pt_msplit.hip)

@@ -278,6 +278,9 @@ struct pqd_plan {
     DevBuf<int> sched, blk_traj, blk_end, blk_sys, blk_act, blk_src, traj_sys, wbeg, wend, ev_start;
     DevBuf<int> blk_fast;         // per block: first step of the lean instance's fast region (block_fast_steps)
     bool lean_ro = false;         // some block of a lean plan has fast steps (pqd_plan_sweep_readout)
+    DevBuf<int> blk_stage;        // per block: the one system whose column operands the fast region stages, or -1
+    int n_stage = 0;              // blocks of a lean plan that stage (pqd_plan_sweep_stage)
+    std::vector<int> h_unit0;     // per wave: the slice of its first PT row unit (< 0: the wave has none)
     int64_t traj_steps = 0;       // executed trajectory-steps per execute (shared trunks counted once)
     int branch = 1;               // shared-trunk activation in the batched sweep (PQD_BRANCH)
     // trunk pre-pass (pqd_host.cpp plan_trunks): one MTO-free trajectory per system writes the checkpoints the
@@ -508,7 +511,7 @@ void pqd_pt_destroy(pqd_pt* pt) { delete pt; }
 struct PlanEnv {
     int split, msplit, ms_tb, ms_ptm, fp4, fpm, pt_mode, cmul3, trpre, bt, colbig, trunk, quad, qpw, qcg, qprio, win,
         rowpair, ablate, hbpt_g;
-    bool ms_l2, split_ow, split_gran, split_xcd, sweep_lean, lean_ro, pt_mode_set, fuse, branch, idle, unitbal, split_l2, hilbert;
+    bool ms_l2, split_ow, split_gran, split_xcd, sweep_lean, lean_ro, lean_stage, pt_mode_set, fuse, branch, idle, unitbal, split_l2, hilbert;
     unsigned split_spin;
 };
 
@@ -528,6 +531,7 @@ static PlanEnv read_plan_env() {
     v.fpm = num("PQD_FPM", 1);                  // N2 = 25, 36 free propagators on the matrix cores (raw value; 0: LDS)
     v.sweep_lean = num("PQD_SWEEP_LEAN", 1) != 0;  // the lean sweep instance where the plan allows it (sweep_lean_ok)
     v.lean_ro = num("PQD_LEAN_RO", 1) != 0;      // lean instance: outputs read inside the fused column phase (0: closure pass)
+    v.lean_stage = num("PQD_LEAN_STAGE", 1) != 0;  // its fast region: next step's F, closure, W staged in LDS (0: loaded in place)
     v.pt_mode_set = set("PQD_PT_MODE");
     v.pt_mode = num("PQD_PT_MODE", 0);          // PT-row variant (raw value; unset: 5 at BT = 4, else 4)
     v.cmul3 = num("PQD_CMUL3", 1);              // 3M column products (raw value)
@@ -910,6 +914,7 @@ static void finalize_trunks(pqd_plan* P) {
     k.ck_map = P->tk_ckmap.p; k.ck_stride = P->n_steps + 1;
     k.lean = 0;
     k.blk_fast = nullptr;
+    k.blk_stage = nullptr;
     const int nw = P->tk_BT * sweep_wpt(P->N2, P->tk_BT, P->CHI);
     k.units = (P->sp.units ? P->tk_units.p : nullptr);
     k.umax = (int)(P->tk_units.n / nw);
@@ -1408,6 +1413,27 @@ static std::vector<int> block_fast_steps(int BT, const Blocks& B, const MtoEvent
     return bf;
 }
 
+// Per block, the system whose column operands F(n + 1), W(n + 1) the fast region stages in LDS during the PT phase of
+// step n (pt_sweep.hip LeanStage): the one system of all its occupied slots, or -1 where the block has no fast region
+// or its slots mix systems (one staging area holds one system's operands; such a block loads them in place as before)
+static std::vector<int> block_stage_systems(int BT, const Blocks& B, const std::vector<int>& tsys,
+                                            const std::vector<int>& blk_fast) {
+    std::vector<int> bs(B.be.size(), -1);
+    for (size_t b = 0; b < B.be.size(); ++b) {
+        if (blk_fast[b] == INT_MAX) continue;
+        int y = -1;
+        bool one = true;
+        for (int q = 0; q < BT; ++q) {
+            const int t = B.bt[b * BT + q];
+            if (t < 0) continue;
+            if (y < 0) y = tsys[t];
+            one = one && tsys[t] == y;
+        }
+        if (one) bs[b] = y;
+    }
+    return bs;
+}
+
 // the free-propagator build of a plan: idle operators and pulse windows. After the trunks: windows need n_trunk == 0
 static int setup_free_props(pqd_plan* P, const pqd_grid* grid, const PlanEnv& env, hipStream_t s) {
     const int n_sys = P->n_sys, ns = P->n_steps;
@@ -1449,7 +1475,7 @@ static int setup_free_props(pqd_plan* P, const pqd_grid* grid, const PlanEnv& en
 // the launch parameters of the main sweep: the plan's buffers, the kernel variants, the PT row units, the fused
 // half steps, and whether the plan runs the lean instance
 static int fill_sweep_params(pqd_plan* P, const pqd_pt* pt, const PlanEnv& env, const std::vector<int>& blk_fast,
-                             hipStream_t s) {
+                             const std::vector<int>& blk_stage, hipStream_t s) {
     const int n_sys = P->n_sys, ns = P->n_steps, N2 = P->N2, n_out = P->n_out;
     const size_t m2 = (size_t)N2 * N2;
     SweepParams& sp = P->sp;
@@ -1490,6 +1516,7 @@ static int fill_sweep_params(pqd_plan* P, const pqd_pt* pt, const PlanEnv& env, 
         P->h_units = fnv1a(u);
         sp.units = P->units.p;
         sp.umax = (int)(u.size() / nw);
+        for (int w = 0; w < nw; ++w) P->h_unit0.push_back(u[(size_t)w * sp.umax].x);
     }
     sp.fuse = (!P->nopt && ns > 0 && env.fuse) ? 1 : 0;
     if (!sp.fuse) sp.trpre = 0;  // the prefetched rows are W(n), which exists only with fused half steps
@@ -1522,6 +1549,16 @@ static int fill_sweep_params(pqd_plan* P, const pqd_pt* pt, const PlanEnv& env, 
         HIPCHK(P->blk_fast.upload(blk_fast.data(), blk_fast.size(), s));
         sp.blk_fast = P->blk_fast.p;
         for (int f : blk_fast) P->lean_ro = P->lean_ro || f != INT_MAX;
+        // the fast region's operands staged a step ahead (PQD_LEAN_STAGE=0: every block loads them in place); allocated
+        // behind blk_fast for the same reason. A wave issues its piece in the first k-step of its first PT unit, so the
+        // six waves with a piece need units (16 rows over 8 waves: they have, unless the row-unit switches leave fewer)
+        bool units_ok = P->h_unit0.size() >= 6;
+        for (int w = 0; units_ok && w < 6; ++w) units_ok = P->h_unit0[w] >= 0;
+        if (env.lean_stage && units_ok) {
+            HIPCHK(P->blk_stage.upload(blk_stage.data(), blk_stage.size(), s));
+            sp.blk_stage = P->blk_stage.p;
+            for (int y : blk_stage) P->n_stage += y >= 0;
+        }
     }
     return PQD_OK;
 }
@@ -1847,7 +1884,7 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
 
     // launch parameters
     if ((rc = setup_free_props(P, grid, env, s))) return rc;
-    if ((rc = fill_sweep_params(P, pt, env, blk_fast, s))) return rc;
+    if ((rc = fill_sweep_params(P, pt, env, blk_fast, block_stage_systems(pc.BT, B, tsys, blk_fast), s))) return rc;
     finalize_trunks(P);
     if (pc.split) {
         HIPCHK(P->Xs.alloc((size_t)n_traj * 4 * N2 * P->CHI));  // split exchange: 2 slots of granules
@@ -2077,6 +2114,12 @@ int pqd_plan_sweep_lean(const pqd_plan* P, int32_t* on) {
 int pqd_plan_sweep_readout(const pqd_plan* P, int32_t* on) {
     if (!P || !on) return fail(PQD_ERR_ARG, "NULL argument");
     *on = (P->sp.lean && P->lean_ro && !P->nopt && !P->split && !P->msplit && !P->quad) ? 1 : 0;
+    return PQD_OK;
+}
+
+int pqd_plan_sweep_stage(const pqd_plan* P, int32_t* n_blocks) {
+    if (!P || !n_blocks) return fail(PQD_ERR_ARG, "NULL argument");
+    *n_blocks = (P->sp.lean && P->lean_ro && !P->nopt && !P->split && !P->msplit && !P->quad) ? P->n_stage : 0;
     return PQD_OK;
 }
 

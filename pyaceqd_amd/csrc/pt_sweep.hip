@@ -23,6 +23,7 @@
 // dominant traffic is L2/MALL-resident; the kernel is FP64 matrix-core bound.
 #include "pqd_common.h"
 #include <climits>
+#include <type_traits>
 
 namespace {
 
@@ -406,6 +407,12 @@ __device__ __forceinline__ void pt_rows3(const double2* __restrict__ Qg, double2
 // 4 ks CHI 16 + 256 g for ks < KSN, g < NG (static_assert below: the largest address is the slice's last element), and
 // the prefetch across units reads k-steps 0 .. PF - 1 of the second unit's own slice, only where that unit exists.
 // Nothing is loaded beyond the slice a unit contracts, whichever slice of the PT's buffer that is.
+// A unit also takes a functor it calls once, in its first k-step between the slice wait and the MFMAs: the fast region
+// issues the staging of the next step's column operands there (LeanStage below), everything else passes LeanNoStage.
+struct LeanNoStage {
+    static constexpr bool ACTIVE = false;
+    __device__ __forceinline__ void operator()() const {}
+};
 template <int CHI, int RS, int TS, int PF>
 struct LeanPt {
     static constexpr int RB = 2, NG = CHI / 16, KSN = CHI / 4;
@@ -444,10 +451,10 @@ struct LeanPt {
     // one unit of R rows: qn holds k-steps 0 .. PF - 1 of its slice Qu on entry and, with MORE, those of the wave's
     // next unit (slice Qnext) on return: the last PF k-steps load them in place of their own slice's.
     // xr, wr: the rows' read and write addresses; avn: k-step 0 of the state rows (issued by the caller)
-    template <int R, bool MORE>
+    template <int R, bool MORE, typename ST>
     static __device__ __forceinline__ void unit(dbl2 (&qn)[PF][NG], const double2* Qu, const double2* Qnext,
                                                 unsigned qoff, const LdsC2* (&xr)[R][RB], LdsC2* (&wr)[R][RB],
-                                                dbl2 (&avn)[R][RB]) {
+                                                dbl2 (&avn)[R][RB], const ST& stg) {
         double p1[R][RB][NG], p2[R][RB][NG], p3[R][RB][NG];
 #pragma unroll
         for (int ks = 0; ks < KSN; ++ks) {
@@ -471,6 +478,15 @@ struct LeanPt {
             double qs[NG];
 #pragma unroll
             for (int g = 0; g < NG; ++g) qs[g] = qv[g].x + qv[g].y;
+            if constexpr (ST::ACTIVE) {
+                // behind the wait for this k-step's slice values (the sums above use them), so that wait does not cover
+                // what stg issues; the next k-step's wait does
+                if (ks == 0) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    stg();
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
 #pragma unroll
             for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -497,9 +513,9 @@ struct LeanPt {
     // (this step's, or the next step's for the first unit of that step). The first row's
     // addresses and its k-step 0 are common to both sizes and issued ahead of the branch (and of the first wait for
     // the slice, which the compiler places there)
-    template <bool MORE>
+    template <bool MORE, typename ST>
     static __device__ __forceinline__ void unit_r(dbl2 (&qn)[PF][NG], const double2* Qs, int4 e, int4 en, unsigned qoff,
-                                                  const double2* xl, double2* wl, const double2* Qns) {
+                                                  const double2* xl, double2* wl, const double2* Qns, const ST& stg) {
         const double2* Qu = Qs + (size_t)e.x * CHI * CHI;
         const double2* Qnext = Qns + (size_t)(MORE ? en.x : e.x) * CHI * CHI;
         const LdsC2* x0[RB];
@@ -522,14 +538,14 @@ struct LeanPt {
                 wr[1][rb] = lds_row((LdsC2*)wl, e.z, rb);
                 avn[1][rb] = xr[1][rb][0];
             }
-            unit<2, MORE>(qn, Qu, Qnext, qoff, xr, wr, avn);
+            unit<2, MORE>(qn, Qu, Qnext, qoff, xr, wr, avn, stg);
         } else {
             const LdsC2* xr[1][RB];
             LdsC2* wr[1][RB];
             dbl2 avn[1][RB];
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) { xr[0][rb] = x0[rb]; wr[0][rb] = w0[rb]; avn[0][rb] = a0[rb]; }
-            unit<1, MORE>(qn, Qu, Qnext, qoff, xr, wr, avn);
+            unit<1, MORE>(qn, Qu, Qnext, qoff, xr, wr, avn, stg);
         }
     }
 
@@ -539,15 +555,19 @@ struct LeanPt {
     // the next PT phase, and every unit body is "in flight at entry, loads a successor at exit". Bounds: k-steps
     // 0 .. PF - 1 of a slice the unit list names, in the set the schedule names for the next step; the caller runs this
     // only where that step is itself a PT step of the block (never in the block's last one)
+    // stg (LeanStageOp or LeanNoStage) is called once per wave, in the first k-step of the wave's first unit. A wave
+    // without units calls nothing: the host stages only where the six waves with a piece have units (blk_stage)
+    template <typename ST>
     static __device__ __forceinline__ void run_pre(dbl2 (&qn)[PF][NG], const double2* Qs, const double2* Qn, int4 u0,
-                                                   int4 u1, unsigned qoff, const double2* xl, double2* wl) {
+                                                   int4 u1, unsigned qoff, const double2* xl, double2* wl, ST stg) {
         if (u0.x < 0) return;
         int4 e = u0;
         if (u1.x >= 0) {
-            unit_r<true>(qn, Qs, u0, u1, qoff, xl, wl, Qs);
+            unit_r<true>(qn, Qs, u0, u1, qoff, xl, wl, Qs, stg);
             e = u1;
+            if constexpr (ST::ACTIVE) stg.ln = 0;
         }
-        unit_r<true>(qn, Qs, e, u0, qoff, xl, wl, Qn);
+        unit_r<true>(qn, Qs, e, u0, qoff, xl, wl, Qn, stg);
     }
     // the wave's units u0 and u1 (slice, row 0, row 1 or -1, -; slice < 0: none) on the step's slice set Qs
     static __device__ __forceinline__ void run(const double2* Qs, int4 u0, int4 u1, unsigned qoff, const double2* xl,
@@ -557,10 +577,10 @@ struct LeanPt {
         ldq_first(qn, Qs + (size_t)u0.x * CHI * CHI, qoff);
         int4 e = u0;
         if (u1.x >= 0) {
-            unit_r<true>(qn, Qs, u0, u1, qoff, xl, wl, Qs);
+            unit_r<true>(qn, Qs, u0, u1, qoff, xl, wl, Qs, LeanNoStage{});
             e = u1;
         }
-        unit_r<false>(qn, Qs, e, e, qoff, xl, wl, Qs);
+        unit_r<false>(qn, Qs, e, e, qoff, xl, wl, Qs, LeanNoStage{});
     }
 };
 
@@ -604,6 +624,86 @@ __device__ __forceinline__ double2 lean_row_sum(double2 v) {
     return c_add(v, make_double2(lean_dpp<0x140>(v.x), lean_dpp<0x140>(v.y)));  // row_mirror
 }
 
+// The column operands of the lean instance's next fast step, staged in LDS while the PT phase runs (the fast region of
+// the step loop). LeanCol opens with 4 + 4 + 4 n_out loads per lane of bytes that are new every step, directly behind the
+// barrier that ends the PT phase: both waves of every SIMD wait out that round trip together before their first MFMA.
+// Fetching them a phase ahead through registers lost to the register file twice, so they go to LDS
+// without passing one: global_load_lds_dwordx4 (16 bytes per lane, no data VGPR) writes lane-linearly from a
+// wave-uniform LDS base, with a source address per lane. Six wave-instructions of at most 1 KiB hold a step's operands:
+//   waves 0..3  F(n + 1) of the block's system in fragment order: wave ks, lane (li, lk) = (lane & 15, lane >> 4) sources
+//               F[li * 16 + 4 ks + lk], the address that lane loads in LeanCol, so LeanCol reads ac[ks] as element
+//               64 ks + lane (1 KiB contiguous per wave read);
+//   wave 4      the 64 elements of the closure vector step n + 1 reads (slice set sched[n]), plainly;
+//   wave 5      the 16 n_out elements of W(n + 1), plainly, by lanes < 16 n_out.
+// The area lies behind rbuf in the dynamic LDS (OFF double2 from its start): F at 0, the closure vector at 256, W at 320
+// (double2 elements), 6 KiB. One area holds one system's operands: a block whose slots mix systems does not stage
+// (SweepParams::blk_stage).
+// Ordering: the loads are issued in the PT phase of step n, behind the barrier that ends column phase n (whose reads of
+// the area LeanCol's closing lgkmcnt(0) retired), in the first k-step of the issuing wave's first unit, after its slice
+// wait and before its MFMAs (LeanPt::unit). Loads return in order, and the k-steps that follow consume slice values
+// loaded behind the staged piece, so the piece has landed long before the wave reaches the barrier that ends the PT
+// phase, and column phase n + 1 reads it behind that barrier. A wave without PT units has no such k-step: the host
+// lets a plan stage only where waves 0..5 have units (pqd_host.cpp fill_sweep_params).
+// The instruction stands in one asm statement: branch-free (the lanes that load are an exec mask, 0 for a wave with
+// nothing to stage), with M0 and exec saved and restored around it, and outside the compiler's vmcnt bookkeeping. An
+// uncounted older load only makes the compiler's counted waits wait for more; counted, the compiler drains vmcnt(0) at the
+// next use of any load and before __syncthreads(), and with it the slice k-step that run_pre keeps in flight.
+// Bounds: every source address is an index expression LeanCol or the step loop loads for a step the block runs (row
+// li < 16, column 4 ks + lk < 16 of F(m), element lane < 64 of a closure vector, element lane < 16 n_out of W(m), for
+// m = n + 1 <= n_end - 2 < n_steps); every destination is area + wave * 1 KiB + lane * 16 B with wave < 6: inside the
+// 6 KiB (static_assert below; launch_sw adds BYTES to the instance's dynamic LDS).
+template <int OFF>
+struct LeanStage {
+    static constexpr int N2 = 16, CHI = 64, KMAX = 4;
+    static constexpr int F_AT = 0, C_AT = N2 * N2, W_AT = C_AT + CHI, ELEMS = W_AT + KMAX * N2;
+    static constexpr size_t BYTES = (size_t)ELEMS * sizeof(double2);
+    typedef double dbl2 __attribute__((ext_vector_type(2)));
+    typedef __attribute__((address_space(3))) dbl2 LdsC2;
+    static_assert(F_AT == 0 && C_AT == 4 * 64 && W_AT == 5 * 64 && ELEMS == 6 * 64 && BYTES == 6144,
+                  "six pieces of 64 lanes x 16 B, wave w's at 64 w elements");
+    static_assert(OFF >= 0 && sizeof(double2) == 16, "16-byte aligned destinations behind the 16-byte aligned smem");
+    static_assert(OFF * sizeof(double2) + BYTES + 512 <= 160 * 1024, "the area fits the LDS beside the static tables");
+
+    static __device__ __forceinline__ LdsC2* area(double2* smem) { return (LdsC2*)(smem + OFF); }
+    // the wave's part, fixed for the launch: the lane's byte offset into its piece's source (F: row li, column
+    // 4 wave + lk; closure vector and W: element lane), the piece's LDS byte address, the lanes that load
+    static __device__ __forceinline__ unsigned lane_off(int wave, int lane) {
+        return (unsigned)((wave < 4 ? (lane & 15) * N2 + 4 * wave + (lane >> 4) : lane) * sizeof(double2));
+    }
+    static __device__ __forceinline__ unsigned dst(double2* smem, int wave) {
+        return (unsigned)(size_t)(area(smem) + 64 * (wave < 6 ? wave : 0));
+    }
+    static __device__ __forceinline__ unsigned long long lanes(int wave, int n_out) {
+        return wave < 5 ? ~0ull : wave > 5 ? 0ull : n_out >= KMAX ? ~0ull : (1ull << (N2 * n_out)) - 1;
+    }
+    // the source of the wave's piece for step m: Fm, Wm: F(m), W(m) of the block's system; cv: the closure vector step m
+    // reads (waves 6, 7 load no lane of it)
+    static __device__ __forceinline__ const double2* src(int wave, const double2* Fm, const double2* cv, const double2* Wm) {
+        return wave < 4 ? Fm : wave == 4 ? cv : Wm;
+    }
+    // one 16-byte element per lane of ln, from base + off (off per lane) to the LDS address to + 16 lane (base, to, ln
+    // wave-uniform)
+    static __device__ __forceinline__ void issue(const double2* base, unsigned off, unsigned to, unsigned long long ln) {
+        unsigned long long keep_exec;
+        unsigned keep_m0;
+        asm volatile("s_mov_b64 %0, exec\n\ts_mov_b32 %1, m0\n\ts_mov_b64 exec, %5\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %1\n\ts_mov_b64 exec, %0"
+                     : "=&s"(keep_exec), "=&s"(keep_m0)
+                     : "v"(off), "s"(base), "s"(to), "s"(ln)
+                     : "memory");
+    }
+};
+// what a wave's first PT unit of a fast step issues behind its first slice wait (LeanPt::unit): its piece of the next
+// step's column operands (ln = 0: nothing, the region's last step and waves 6, 7)
+template <typename LS>
+struct LeanStageOp {
+    static constexpr bool ACTIVE = true;
+    const double2* base;
+    unsigned off, to;
+    unsigned long long ln;
+    __device__ __forceinline__ void operator()() const { LS::issue(base, off, to, ln); }
+};
+
 // The fused column operator F(n) of the lean instance with the step's outputs read on the way (N2 = 16, chi = 64, one
 // wave per trajectory). The state the outputs of a fused step are read from is the one before F(n), and the wave that
 // applies F(n) loads exactly those values as its B operands: lane (li, lk) = (lane & 15, lane >> 4) holds
@@ -617,31 +717,42 @@ __device__ __forceinline__ double2 lean_row_sum(double2 v) {
 // and every write S[lk + 4 r][16 nt + li] at base + (4 j RS + 16 nt) 16 B, j < 4: the DS immediate (largest 12 RS 16 + 768).
 // Bounds: F, W and the closure vector are indexed as the step loop's own loads of them (row li < 16 and column
 // 4 ks + lk < 16 of F(n), n < n_steps; W(n)[k][4 ks + lk], k < n_out; c[16 nt + li] < CHI of slice set sched[n - 1]).
-template <int RS, bool READOUT>
+// STAGED: Fn, cv and Wn are the parts of the LDS area LeanStage filled during the PT phase before (F in fragment order,
+// element 64 ks + lane; the closure vector and W as in memory, the same indices as the global loads: < 64 and
+// < 16 n_out <= 64), the same values in the same registers, so nothing downstream differs.
+template <int RS, bool READOUT, bool STAGED = false>
 struct LeanCol {
     static constexpr int N2 = 16, CHI = 64, KS = 4, NTL = 4, KMAX = 4;   // KMAX: the lean instance's limit on n_out
     typedef double dbl2 __attribute__((ext_vector_type(2)));
     typedef __attribute__((address_space(3))) dbl2 LdsC2;
     static_assert((12 * RS + 48) * 16 + 15 < 65536, "tile and row offsets fit the DS immediate");
+    // where the operands come from: global memory (restrict: nothing here writes it), or the staging area
+    template <bool S, typename = void> struct SrcOf { typedef const double2* __restrict__ type; };
+    template <typename V> struct SrcOf<true, V> { typedef const LdsC2* type; };
+    typedef typename SrcOf<STAGED>::type Src;
+    static __device__ __forceinline__ double2 ld(Src q, int i) {
+        const auto v = q[i];
+        return make_double2(v.x, v.y);
+    }
 
+    // (W(n) stays loaded ahead of the tiles in both forms: read from the staging area behind the last tile's operands
+    // instead, it measured the same)
     // Fn: F(n) of the wave's system; cv: closure vector of the slice set of step n - 1; Wn: W(n) of the wave's system;
     // sb: the lane's LDS base; out: where the slot's n_out outputs of step n go (READOUT only)
-    static __device__ __forceinline__ void run(const double2* __restrict__ Fn, const double2* __restrict__ cv,
-                                               const double2* __restrict__ Wn, int n_out, LdsC2* sb, double2* out,
-                                               int lane) {
+    static __device__ __forceinline__ void run(Src Fn, Src cv, Src Wn, int n_out, LdsC2* sb, double2* out, int lane) {
         const int li = lane & 15, lk = lane >> 4;
         double2 ac[KS], cl[NTL], w[KMAX][KS];
         double as[KS];
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) ac[ks] = Fn[li * N2 + 4 * ks + lk];
+        for (int ks = 0; ks < KS; ++ks) ac[ks] = ld(Fn, STAGED ? 64 * ks + lane : li * N2 + 4 * ks + lk);
         if constexpr (READOUT) {
 #pragma unroll
-            for (int nt = 0; nt < NTL; ++nt) cl[nt] = cv[16 * nt + li];
+            for (int nt = 0; nt < NTL; ++nt) cl[nt] = ld(cv, 16 * nt + li);
 #pragma unroll
             for (int k = 0; k < KMAX; ++k)
                 if (k < n_out) {
 #pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) w[k][ks] = Wn[k * N2 + 4 * ks + lk];
+                    for (int ks = 0; ks < KS; ++ks) w[k][ks] = ld(Wn, k * N2 + 4 * ks + lk);
                 }
         }
 #pragma unroll
@@ -912,27 +1023,68 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
                     sb = (typename LC::LdsC2*)v;
                 }
                 const bool occupied = my_act != INT_MAX;
-                // the first k-step of the wave's first unit, in flight from one step's PT phase to the next's
+                // A block whose slots share one system (SweepParams::blk_stage) takes F(n), the closure vector and W(n) from
+                // LDS: the PT phase of step n - 1 staged them (LeanStage), and a prologue those of the region's first step.
+                // The region's last PT phase stages nothing: step n_end - 1 loads for itself below. The two forms are two
+                // loops (STG), so that neither carries the other's operands
                 using LP = LeanPt<CHI, RS, TS, LEAN_PF>;
-                typename LP::dbl2 qn[LEAN_PF][CHI / 16];
-                if (u0.x >= 0) LP::ldq_first(qn, Qg0 + ((size_t)sc_cur * p.D + u0.x) * CHI * CHI, lean_qoff);
-                for (; n < n_end - 1; ++n) {
-                    sc_nxt = ldc(p.sched + (n + 1 < p.n_steps ? n + 1 : p.n_steps - 1));
-                    if (occupied) {
-                        const double2* Fn = Fg + (size_t)n * N2 * N2;
-                        if (w_beg <= n && n <= w_end)   // the store's predicate: the slot's window, wave-uniform
-                            LC::run(Fn, p.closure + (size_t)sc_prev * CHI, Ww + (size_t)n * p.n_out * N2, p.n_out, sb,
-                                    outg + w_off + (long long)(n - w_beg) * p.n_out, lane);
-                        else
-                            LeanCol<RS, false>::run(Fn, nullptr, nullptr, 0, sb, nullptr, lane);
+                using LS = LeanStage<BT * TS + BT * N2>;
+                const int st_sys = p.blk_stage ? ldc(p.blk_stage + blockIdx.x) : -1;
+                auto fast_steps = [&](auto stc) {
+                    constexpr bool STG = decltype(stc)::value;
+                    typename LS::LdsC2* sg = LS::area(smem);
+                    const double2* Fst = p.F + (size_t)(STG ? st_sys : 0) * p.f_stride;
+                    const double2* Wst = Wg + (size_t)(STG ? st_sys : 0) * p.w_stride;
+                    const unsigned st_off = LS::lane_off(wave, lane), st_to = LS::dst(smem, wave);
+                    const unsigned long long st_ln = LS::lanes(wave, p.n_out);
+                    if constexpr (STG) {
+                        LS::issue(LS::src(wave, Fst + (size_t)n * N2 * N2, p.closure + (size_t)sc_prev * CHI,
+                                          Wst + (size_t)n * p.n_out * N2), st_off, st_to, st_ln);
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        __syncthreads();
                     }
-                    __syncthreads();
-                    LP::run_pre(qn, Qg0 + (size_t)sc_cur * p.D * CHI * CHI, Qg0 + (size_t)sc_nxt * p.D * CHI * CHI, u0, u1,
-                                lean_qoff, lean_xl, lean_wl);
-                    __syncthreads();
-                    sc_prev = sc_cur;
-                    sc_cur = sc_nxt;
-                }
+                    // the first k-step of the wave's first unit, in flight from one step's PT phase to the next's
+                    typename LP::dbl2 qn[LEAN_PF][CHI / 16];
+                    if (u0.x >= 0) LP::ldq_first(qn, Qg0 + ((size_t)sc_cur * p.D + u0.x) * CHI * CHI, lean_qoff);
+                    for (; n < n_end - 1; ++n) {
+                        sc_nxt = ldc(p.sched + (n + 1 < p.n_steps ? n + 1 : p.n_steps - 1));
+                        if (occupied) {
+                            const bool inwin = w_beg <= n && n <= w_end;   // the store's predicate: the slot's window, wave-uniform
+                            if constexpr (STG) {
+                                if (inwin)
+                                    LeanCol<RS, true, true>::run(sg + LS::F_AT, sg + LS::C_AT, sg + LS::W_AT, p.n_out, sb,
+                                                                 outg + w_off + (long long)(n - w_beg) * p.n_out, lane);
+                                else
+                                    LeanCol<RS, false, true>::run(sg + LS::F_AT, nullptr, nullptr, 0, sb, nullptr, lane);
+                            } else {
+                                const double2* Fn = Fg + (size_t)n * N2 * N2;
+                                if (inwin)
+                                    LC::run(Fn, p.closure + (size_t)sc_prev * CHI, Ww + (size_t)n * p.n_out * N2, p.n_out, sb,
+                                            outg + w_off + (long long)(n - w_beg) * p.n_out, lane);
+                                else
+                                    LeanCol<RS, false>::run(Fn, nullptr, nullptr, 0, sb, nullptr, lane);
+                            }
+                        }
+                        __syncthreads();
+                        if constexpr (STG) {
+                            // step n + 1 <= n_end - 2 reads the closure vector of sched[n]
+                            const LeanStageOp<LS> stg{LS::src(wave, Fst + (size_t)(n + 1) * N2 * N2,
+                                                              p.closure + (size_t)sc_cur * CHI,
+                                                              Wst + (size_t)(n + 1) * p.n_out * N2),
+                                                      st_off, st_to, n + 2 < n_end ? st_ln : 0ull};
+                            LP::run_pre(qn, Qg0 + (size_t)sc_cur * p.D * CHI * CHI, Qg0 + (size_t)sc_nxt * p.D * CHI * CHI, u0,
+                                        u1, lean_qoff, lean_xl, lean_wl, stg);
+                        } else {
+                            LP::run_pre(qn, Qg0 + (size_t)sc_cur * p.D * CHI * CHI, Qg0 + (size_t)sc_nxt * p.D * CHI * CHI, u0,
+                                        u1, lean_qoff, lean_xl, lean_wl, LeanNoStage{});
+                        }
+                        __syncthreads();
+                        sc_prev = sc_cur;
+                        sc_cur = sc_nxt;
+                    }
+                };
+                if (st_sys >= 0) fast_steps(std::true_type{});
+                else fast_steps(std::false_type{});
                 fz = true;
                 if (tid < ntr) {  // W(n_end - 1) row element for the traces below
                     const int a = tid % N2, bk = tid / N2, b = bk / p.n_out, k = bk - (bk / p.n_out) * p.n_out;
@@ -1270,17 +1422,20 @@ __global__ __launch_bounds__(64) void sweep_nopt_kernel(SweepParams p) {
 template <int N2, int CHI, int BT, bool TRUNK, bool LEAN = false>
 hipError_t launch_sw(int n_blocks, const SweepParams& p, hipStream_t s) {
     using L = SweepLayout<N2, CHI, BT>;
-    static_assert(L::LDS <= 160 * 1024, "LDS budget");
+    // the lean instance: the staging area of its fast region behind rbuf (LeanStage; 6 KiB of the 27.8 KiB left)
+    constexpr size_t LDS = L::LDS + (LEAN ? LeanStage<BT * L::TS + BT * N2>::BYTES : 0);
+    static_assert((BT * L::TS + BT * N2) * sizeof(double2) == L::LDS, "the area starts where the states and rbuf end");
+    static_assert(LDS + 512 <= 160 * 1024, "LDS budget (512 B: the kernel's static tables)");
     static unsigned attr = 0;  // per-device bitmask (the attribute belongs to the device's copy of the kernel)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
     if (dev >= 32 || !(attr & (1u << dev))) {
         hipError_t e = hipFuncSetAttribute((const void*)pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::LDS);
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
         if (e != hipSuccess) return e;
         if (dev < 32) attr |= 1u << dev;
     }
-    hipLaunchKernelGGL((pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN>), dim3(n_blocks), dim3(64 * L::NW), L::LDS, s, p, p.M,
+    hipLaunchKernelGGL((pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN>), dim3(n_blocks), dim3(64 * L::NW), LDS, s, p, p.M,
                        p.Q, p.out, p.F, p.W);
     return hipGetLastError();
 }

@@ -515,6 +515,13 @@ class Plan:
         _lib.check(_lib.lib().pqd_plan_sweep_readout(self.handle, C.byref(on)))
         return bool(on.value)
 
+    def sweep_stage(self):
+        """the number of workgroups whose fast steps (sweep_readout) take F(n), W(n) and the closure vector from LDS,
+        staged there a step ahead: those whose trajectories share one system (PQD_LEAN_STAGE=0: none)"""
+        n = C.c_int32()
+        _lib.check(_lib.lib().pqd_plan_sweep_stage(self.handle, C.byref(n)))
+        return int(n.value)
+
     def describe(self):
         """every decision plan creation took (pqd_plan_describe) as a dict of strings: path, workgroup shape, split /
         quad / trunk layout, windows, the A/B switches, and hashes of the block, row-unit and group tables"""
