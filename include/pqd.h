@@ -358,9 +358,20 @@ int pqd_map_tail(pqd_ctx* ctx, const pqd_c128* M, int32_t N2, const pqd_c128* X,
 /* ---- time-local dynamical maps (replaces tools.calc_tl_dynmap_pseudo, reference tools.py:446-484) ----
  * dm: n_maps row-major n x n maps, dm[i] = E(t_{i+1}, t0). out (n_maps maps): out[0] = dm[0],
  * out[i] = dm[i] pinv(dm[i-1]) with singular values <= rcond * max(s) dropped (numpy pinv, rcond
- * 1e-12 in the reference). n <= 36 (N <= 6). */
+ * 1e-12 in the reference). 1 <= n <= 576 (N <= 24; any n, not only squares): n <= 36 on the single-wave
+ * kernel (tlmap.hip), 37 <= n <= 576 on the block-Jacobi kernel (tlmap_wide.hip), whose workspace is sized
+ * by its persistent grid, not by n_maps. n_maps == 0 returns PQD_OK without touching the device.
+ * PQD_ERR_ARG: a NULL argument, n_maps < 0, rcond negative or NaN. PQD_ERR_UNSUPPORTED: n < 1 or n > 576
+ * ("map size %d (max 576)"). PQD_ERR_NOMEM: the input maps, the output maps (n_maps n^2 16 bytes each) or
+ * the workspace cannot be allocated; the message names the bytes asked for. PQD_ERR_NUMERIC (n >= 37; out
+ * still copied): a map's Jacobi SVD was still rotating after 40 sweeps, or a singular value was not finite.
+ * pqd_tl_dynmap_timing: duration (ms, HIP events) of the kernel of the context's last pqd_tl_dynmap_pseudo
+ * call (either kernel); PQD_ERR_ARG before any call has completed. pqd_tl_dynmap_sweeps: the largest sweep
+ * count over the maps of that call (-1 after the n <= 36 kernel, which does not report it). */
 int pqd_tl_dynmap_pseudo(pqd_ctx* ctx, const pqd_c128* dm, int32_t n_maps, int32_t n, double rcond,
                          pqd_c128* out);
+int pqd_tl_dynmap_timing(pqd_ctx* ctx, double* ms_kernel);
+int pqd_tl_dynmap_sweeps(pqd_ctx* ctx, int32_t* max_sweeps);
 
 /* ---- PT generator factorizations (replaces the factorizations inside `ACE <generate.param>` with
  * `dont_propagate true` + `write_PT`, reference general_system.py:152-211; driven by pyaceqd_amd/ptgen_gpu.py,

@@ -447,6 +447,13 @@ hipError_t launch_map_tail(int N2, const double2* M, const double2* X, int n_x, 
                            double2* out, hipStream_t s);
 hipError_t launch_tl_dynmap(const double2* dm, int n_maps, int n, double rcond, double2* out, hipStream_t s);
 int tl_dynmap_nmax();
+// tlmap_wide.hip: map sizes tl_dynmap_wide_nmin() .. tl_dynmap_wide_nmax(). _plan gives the persistent grid and the
+// workspace (in double2) that _wide wants; flags: bit 0 non-finite, bit 1 not converged; sweeps: the largest count
+int tl_dynmap_wide_nmin();
+int tl_dynmap_wide_nmax();
+hipError_t tl_dynmap_wide_plan(int n, int n_maps, int n_cu, int* grid, size_t* ws_elems);
+hipError_t launch_tl_dynmap_wide(const double2* dm, int n_maps, int n, double rcond, double2* out, double2* ws,
+                                 int grid, unsigned* flags, int* sweeps, hipStream_t s);
 // ow: split groups have the output workgroup (SweepParams.split_ow; pqd_host.cpp PlanEnv)
 bool split_supported(int N2, int CHI, int n_traj, int n_cu, bool ow);
 int split_group_size(int N2, bool ow);  // workgroups per split group (N2, or N2 + 1 with the output workgroup)

@@ -187,6 +187,8 @@ struct pqd_ctx {
     DevBuf<char> mc_arena;
     double dressed_ms = -1.0;  // kernel duration of the last pqd_dressed_states call (pqd_dressed_timing)
     double dynmap_ms = -1.0;   // duration of the map instance of the last pqd_dynmap_wide call (pqd_dynmap_timing)
+    double tlmap_ms = -1.0;    // kernel duration of the last pqd_tl_dynmap_pseudo call (pqd_tl_dynmap_timing)
+    int tlmap_sweeps = -1;     // its largest Jacobi sweep count (tlmap_wide.hip; -1 after the n <= 36 kernel)
 };
 
 namespace {
@@ -2693,20 +2695,85 @@ int pqd_dynamics_t1(pqd_ctx* ctx, const pqd_c128* dm_1, const pqd_c128* dm_2, co
 int pqd_tl_dynmap_pseudo(pqd_ctx* ctx, const pqd_c128* dm, int32_t n_maps, int32_t n, double rcond,
                          pqd_c128* out) {
     if (!ctx || !dm || !out) return fail(PQD_ERR_ARG, "NULL argument");
-    if (n < 1 || n > tl_dynmap_nmax()) return fail(PQD_ERR_UNSUPPORTED, "map size %d (max %d)", n, tl_dynmap_nmax());
+    if (n < 1 || n > tl_dynmap_wide_nmax())
+        return fail(PQD_ERR_UNSUPPORTED, "map size %d (max %d)", n, tl_dynmap_wide_nmax());
     if (n_maps < 0) return fail(PQD_ERR_ARG, "n_maps %d", n_maps);
     if (!(rcond >= 0.0)) return fail(PQD_ERR_ARG, "rcond %g", rcond);
     if (n_maps == 0) return PQD_OK;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
+    const bool wide = n > tl_dynmap_nmax();   // tlmap_wide.hip; up to tl_dynmap_nmax() the single-wave kernel as before
     const size_t m2 = (size_t)n * n;
-    DevBuf<double2> d, o;
-    HIPCHK(d.upload(reinterpret_cast<const double2*>(dm), (size_t)n_maps * m2, s));
-    HIPCHK(o.alloc((size_t)n_maps * m2));
+    const size_t total = (size_t)n_maps * m2;
+    int grid = 0;
+    size_t ws_elems = 0;
+    if (wide) {
+        int n_cu = 256;
+        if (hipDeviceProp_t prop; hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) n_cu = prop.multiProcessorCount;
+        HIPCHK(tl_dynmap_wide_plan(n, n_maps, n_cu, &grid, &ws_elems));
+    }
+    DevBuf<double2> d, o, ws;
+    DevBuf<unsigned> aux;   // [0] the flags, [1] the largest sweep count
+    auto nomem = [&](hipError_t e, const char* what, size_t elems) {
+        return fail(e == hipErrorOutOfMemory ? PQD_ERR_NOMEM : PQD_ERR_HIP, "%s of %zu bytes: %s", what,
+                    elems * sizeof(double2), hipGetErrorString(e));
+    };
+    if (hipError_t e = d.alloc(total); e != hipSuccess) return nomem(e, "input maps", total);
+    if (hipError_t e = o.alloc(total); e != hipSuccess) return nomem(e, "output maps", total);
+    if (wide) {
+        if (hipError_t e = ws.alloc(ws_elems); e != hipSuccess) return nomem(e, "Jacobi workspace", ws_elems);
+        HIPCHK(aux.alloc(2));
+        HIPCHK(hipMemsetAsync(aux.p, 0, 2 * sizeof(unsigned), s));
+    }
+    HIPCHK(hipMemcpyAsync(d.p, dm, total * sizeof(double2), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(o.p, d.p, m2 * sizeof(double2), hipMemcpyDeviceToDevice, s));  // out[0] = dm[0]
-    HIPCHK(launch_tl_dynmap(d.p, n_maps, n, rcond, o.p, s));
-    HIPCHK(hipMemcpyAsync(out, o.p, (size_t)n_maps * m2 * sizeof(double2), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+
+    hipEvent_t ev[2];
+    HIPCHK(hipEventCreate(&ev[0]));
+    if (hipError_t e1 = hipEventCreate(&ev[1]); e1 != hipSuccess) {
+        (void)hipEventDestroy(ev[0]);
+        return fail(PQD_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e1));
+    }
+    auto run = [&]() -> int {
+        unsigned res[2] = {0u, 0u};
+        HIPCHK(hipEventRecord(ev[0], s));
+        if (wide)
+            HIPCHK(launch_tl_dynmap_wide(d.p, n_maps, n, rcond, o.p, ws.p, grid, aux.p,
+                                         reinterpret_cast<int*>(aux.p + 1), s));
+        else
+            HIPCHK(launch_tl_dynmap(d.p, n_maps, n, rcond, o.p, s));
+        HIPCHK(hipEventRecord(ev[1], s));
+        if (wide) HIPCHK(hipMemcpyAsync(res, aux.p, sizeof res, hipMemcpyDeviceToHost, s));
+        touch_pages(out, total * sizeof(double2));
+        HIPCHK(hipMemcpyAsync(out, o.p, total * sizeof(double2), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        ctx->tlmap_ms = ms;
+        ctx->tlmap_sweeps = wide ? (int)res[1] : -1;
+        // the maps are handed over all the same (they show where the run went bad)
+        if (res[0] & 1u) return fail(PQD_ERR_NUMERIC, "non-finite value (NaN/Inf) in the singular values of a map");
+        if (res[0] & 2u)
+            return fail(PQD_ERR_NUMERIC, "the Jacobi SVD of a map was still rotating after %d sweeps", (int)res[1]);
+        return PQD_OK;
+    };
+    const int rc = run();
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    return rc;
+}
+
+int pqd_tl_dynmap_timing(pqd_ctx* ctx, double* ms_kernel) {
+    if (!ctx || !ms_kernel) return fail(PQD_ERR_ARG, "NULL argument");
+    if (ctx->tlmap_ms < 0) return fail(PQD_ERR_ARG, "no pqd_tl_dynmap_pseudo call has completed on this context");
+    *ms_kernel = ctx->tlmap_ms;
+    return PQD_OK;
+}
+
+int pqd_tl_dynmap_sweeps(pqd_ctx* ctx, int32_t* max_sweeps) {
+    if (!ctx || !max_sweeps) return fail(PQD_ERR_ARG, "NULL argument");
+    if (ctx->tlmap_ms < 0) return fail(PQD_ERR_ARG, "no pqd_tl_dynmap_pseudo call has completed on this context");
+    *max_sweeps = ctx->tlmap_sweeps;
     return PQD_OK;
 }
 

@@ -184,9 +184,12 @@ def calc_tl_dynmap_pseudo(dm, times, debug=False):
     """Time-local maps E(t_{i+1}, t_i) = E(t_{i+1}, t0) pinv(E(t_i, t0)) from cumulative maps dm[i] = E(t_{i+1}, t0)
     (reference tools.py:446-484): out[0] = dm[0], out[i] = dm[i] pinv(dm[i-1], rcond=1e-12), len(times)-1 maps.
 
-    Runs on the GPU (libpqd `pqd_tl_dynmap_pseudo`: one Jacobi SVD per map, one workgroup each). The reference's
-    LinAlgError retry without rcond has no counterpart: the Jacobi SVD does not fail to converge; `debug` is
-    accepted for signature compatibility."""
+    Runs on the GPU (libpqd `pqd_tl_dynmap_pseudo`: one one-sided Jacobi SVD per map, one workgroup each). Map sizes
+    n = dm.shape[1] up to 576 (Hilbert dimension up to 24): n <= 36 on the single-wave kernel with the map in LDS,
+    37 <= n <= 576 on the block-Jacobi kernel (`csrc/tlmap_wide.hip`); the C side picks. Larger maps
+    raise `PQDError` (unsupported). The reference's LinAlgError retry without rcond has no counterpart: above n = 36
+    a map whose SVD is still rotating after 40 sweeps, or a non-finite singular value, raises `PQDError` (numeric);
+    `debug` is accepted for signature compatibility."""
     from . import _lib
     dm = np.ascontiguousarray(dm, dtype=np.complex128)
     n_out = len(times) - 1
