@@ -362,7 +362,30 @@ struct HilbertParams {
     const double* map_ta;    // n_maps start times
     int map_steps, map_nev;
 };
-size_t hilbert_csr_bytes(int N, int n_lind, int nnz);  // LDS bytes of one system's nonzero lists (a multiple of 16)
+// LDS bytes of one system's nonzero lists: values, gamma conj(values), then columns, then row offsets (a multiple of 16)
+constexpr size_t hilbert_csr_bytes(int N, int n_lind, int nnz) {
+    return ((size_t)nnz * 2 * sizeof(double2) + ((size_t)nnz + (size_t)n_lind * (N + 1)) * sizeof(int) + 15) & ~(size_t)15;
+}
+// LDS matrices (16-byte elements) of one trajectory: R, T, Tn, K, Kd, B_0 .. B_{nl_max-1}; threads of one matrix
+constexpr size_t hb_mat_elems(int N, int nl_max) { return (size_t)(5 + nl_max) * N * N; }
+constexpr int hb_threads(int N) { return (N * N + 63) / 64 * 64; }  // one per element, whole waves
+// what every Hilbert-space launcher requires of p, and the map instances of p and n_traj on top of it
+inline bool hb_params_ok(const HilbertParams& p) {
+    return p.N >= 2 && p.N <= HB_NMAX && p.nl_max >= 0 && p.nl_max <= HB_LMAX && p.csr_lds >= 0 && p.csr_lds <= HB_CSR_LDS;
+}
+inline bool hb_map_params_ok(const HilbertParams& p, int n_traj) {
+    return n_traj % (p.N * p.N) == 0 && p.map_ta && p.map_steps >= 1 && p.map_nev >= 0 && p.out;
+}
+// allows `kernel` lds bytes of dynamic LDS on the current device, unless `allowed` (the kernel's own record, one entry
+// per device: the attribute belongs to the device's copy of the kernel) shows it has that much already
+inline hipError_t hb_allow_lds(const void* kernel, size_t (&allowed)[32], size_t lds) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
+    if (dev < 32 && lds <= allowed[dev]) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess && dev < 32) allowed[dev] = lds;
+    return e;
+}
 hipError_t launch_hilbert(int n_traj, const HilbertParams& p, hipStream_t s);
 hipError_t launch_hilbert_map(int n_traj, const HilbertParams& p, hipStream_t s);  // n_traj = n_maps * N^2
 // dm[m][n][alpha][beta] = stage[((m N^2 + beta) n_steps + n) N^2 + alpha]: the states the map instances stored, as

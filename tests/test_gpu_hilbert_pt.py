@@ -142,6 +142,28 @@ def test_structured_pt_leaves_the_physics_unchanged():
     _check(got, engine.propagate(sysd, grid, rho0, ops, tr), "structured PT vs no PT")
 
 
+@pytest.mark.parametrize("N,n_sub", [(7, 1), (9, 2)])
+def test_a_trivial_pt_gives_the_bits_of_the_run_without_a_pt(N, n_sub):
+    """chi = 1, D = 1, every slice Q = [[1]], closures and bond0 = 1: what the PT kernel does beyond the shared step
+    (lind_hilbert_step.h) is a multiplication by 1 or an addition of 0, and the output sums run in the same order
+    whichever wave takes them, so the result is that of lind_hilbert_kernel bit for bit"""
+    n_steps = 6
+    sysd, grid = H.random_system(N, n_chan=2, n_lind=2, n_steps=n_steps, dt=0.1, n_sub=n_sub, seed=N)
+    rng = np.random.default_rng(300 + N)
+    tr = Trajectories(np.array([0, 2]), np.array([n_steps - 1, n_steps]), _mtos(rng, N, n_steps))
+    ops = [_dense(rng, N) for _ in range(3)]
+    rho0 = H.random_rho(N)
+    one = np.ones(1, dtype=np.complex128)
+    pt = engine.ProcessTensor(Q=np.ones((1, 1, 1, 1), dtype=np.complex128), closure=one[None, :], closure0=one,
+                              bond0=one, gmap=np.zeros(N * N, dtype=np.int32), n_init=0)
+    got = engine.propagate(sysd, grid, rho0, ops, tr, pt=pt, wide_pt=True)
+    want = engine.propagate(sysd, grid, rho0, ops, tr)
+    assert len(got) == len(want) == 2
+    for a, b in zip(got, want):
+        assert np.all(np.isfinite(b)) and np.max(np.abs(b)) > 0
+        assert np.array_equal(a, b)
+
+
 def test_alone_and_in_a_batch_of_70_are_byte_equal():
     N, chi, n_steps, n_traj = 7, 5, 5, 70
     systems = [H.random_system(N, n_steps=n_steps, seed=60 + k, n_lind=1 + k)[0] for k in range(3)]
