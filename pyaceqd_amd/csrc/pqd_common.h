@@ -499,5 +499,18 @@ bool quad_supported(int N2, int CHI);
 int quad_qpw(int CHI, int qpw, int ncg);  // quads per workgroup launch_quad instantiates
 hipError_t launch_quad(int CHI, int n_quads, int qpw, int ncg, const SweepParams& p, hipStream_t s);
 
+// consecutive 256-B aligned sub-buffers of one device allocation (size pass with base == nullptr)
+struct Carve {
+    char* base = nullptr;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t count) {
+        off = (off + 255) & ~(size_t)255;
+        T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += count * sizeof(T);
+        return r;
+    }
+};
+
 // thread-local last error shared by the host translation units (pqd_host.cpp owns it); returns code
 extern "C" int pqd_fail_msg(int code, const char* msg);

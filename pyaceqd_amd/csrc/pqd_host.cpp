@@ -220,19 +220,6 @@ void touch_pages(void* buf, size_t bytes) {
     for (auto& t : th) t.join();
 }
 
-// consecutive 256-B aligned sub-buffers of one device allocation (size pass with base == nullptr)
-struct Carve {
-    char* base = nullptr;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += count * sizeof(T);
-        return r;
-    }
-};
-
 // 64-bit FNV-1a over a host array's bytes, chained through h (the table hashes of pqd_plan_describe)
 template <class T>
 uint64_t fnv1a(const std::vector<T>& v, uint64_t h = 14695981039346656037ull) {

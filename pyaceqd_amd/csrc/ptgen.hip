@@ -19,6 +19,14 @@
 //     truncation (1e-10 relative) sees the same spectrum LAPACK's SVD does.
 //   * single-workgroup variants of all three for matrices that fit in LDS (the far, small-bond sites).
 //
+// Steps that several kernel variants take exist once, as __forceinline__ device functions ahead of the kernels:
+// apply_refl_wave (one wave applies one reflector to one column), pivot_search / pivot_limit / phys_col (the pivot, the
+// stop rule, the swap), jac_angle (the rotation decision and angle), grid_meet (the persistent kernels'
+// grid barrier). The register-resident variants (EPT / QE / EPL > 0) keep their own bodies around those: their
+// arithmetic is fused with their loads. On the host: read_ptg_env (every PQD_PTG_* switch, read once per call),
+// dispatch_pow2 (the kernel instance for a runtime EPT / QE / EPL), choose_qr_path, Carve (pqd_common.h) for the scratch
+// layout, and one function per path under the two entry points.
+//
 // Layout: every matrix is column-major with leading dimension = rows (a row-major torch tensor of shape
 // (cols, rows) whose row j is column j). Complex numbers are double2 (pqd_c128).
 #include "pqd_common.h"
@@ -31,6 +39,8 @@
 #include <cstring>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -91,6 +101,110 @@ __device__ __forceinline__ Refl make_refl(double2 alpha, double xn2) {
     return r;
 }
 
+// One wave applies reflector i, v = (1 at row i; x[r] * scale below it), to a column: col <- col - t v (v^H col) on rows
+// >= i, with t = conj(tau) (herm: H^H, the trailing update of a factorization) or tau (H, Q formation). Three strided
+// passes over rows > i: the dot product, the update, and lane 0 writes row i. want_norm: returns |col[i+1:]|^2 after the
+// update in every lane (the trailing norm the next pivot search reads), else 0.
+__device__ __forceinline__ double apply_refl_wave(const double2* x, double2 scale, double2 tau, bool herm, double2* col,
+                                                  int i, int m, int lane, bool want_norm = false) {
+    const double2 ci0 = col[i];
+    double2 s = c_zero();
+    for (int r = i + 1 + lane; r < m; r += 64) {
+        const double2 v = c_mul(x[r], scale);
+        const double2 cr = col[r];
+        s.x += v.x * cr.x + v.y * cr.y;
+        s.y += v.x * cr.y - v.y * cr.x;
+    }
+    s = wsum2(s);
+    s = c_add(s, ci0);
+    const double2 t = herm ? c_cmul(tau, s) : c_mul(tau, s);
+    double nn = 0.0;
+    for (int r = i + 1 + lane; r < m; r += 64) {
+        const double2 v = c_mul(x[r], scale);
+        double2 cr = col[r];
+        cr = c_sub(cr, c_mul(t, v));
+        col[r] = cr;
+        nn += c_abs2(cr);
+    }
+    if (lane == 0) col[i] = c_sub(ci0, t);
+    return want_norm ? wsum(nn) : 0.0;
+}
+
+// Pivot search of step k, by one wave: the logical column j in [k, n) with the largest trailing norm^2 norm_of(j), ties
+// to the lower index; every lane gets the result. norm_of is a plain load of norms[perm[j]] in the kernels that read
+// what an earlier launch or an LDS barrier made visible, an agent-scope atomic load in the persistent kernel.
+struct Pivot {
+    double best;
+    int j;
+};
+template <class NormOf>
+__device__ __forceinline__ Pivot pivot_search(int k, int n, int lane, NormOf norm_of) {
+    double best = -1.0;
+    int bj = k;
+    for (int j = k + lane; j < n; j += 64) {
+        const double v = norm_of(j);
+        if (v > best) { best = v; bj = j; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o);
+        const int oj = __shfl_xor(bj, o);
+        if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
+    }
+    return Pivot{best, bj};
+}
+// The stop rule: the factorization ends at step k when the pivot's norm^2 is <= this. Absolute mode: tol2. Relative mode
+// (rel2 > 0): rel2 x the largest column norm^2 of W, which step 0's search sees; kept in *thr for the later steps (a
+// device word written by `writer` in the one-launch-per-step kernels, a register where every step runs in one launch).
+__device__ __forceinline__ double pivot_limit(int k, double tol2, double rel2, double best, double* thr, bool writer) {
+    if (!(rel2 > 0.0)) return tol2;
+    if (k > 0) return *thr;
+    const double lim = rel2 * best;
+    if (writer) *thr = lim;
+    return lim;
+}
+// physical column of logical column j once step k has swapped logical columns k and p (pin: the permutation before it)
+__device__ __forceinline__ int phys_col(bool pivot, const int* pin, int k, int p, int j) {
+    if (!pivot) return j;
+    return j == k ? pin[p] : (j == p ? pin[k] : pin[j]);
+}
+
+// Grid barrier of the persistent kernels (hand-off as in pt_split.hip): every wave drains its stores (s_waitcnt
+// vmcnt(0)), the workgroup meets, thread 0 adds *add_count (LDS) to *add_word if `add` (a sweep's rotation count, which
+// must be visible before the arrival), drains again and adds one arrival to the monotonic counter *bar; the first wave
+// polls it (s_sleep between polls) until it reaches target = workgroups x barriers so far. A wait of more than
+// spin_limit polls (workgroups not co-resident) sets *s_abort (LDS, zeroed by the caller) and *err; returns false and
+// every workgroup leaves, since each of them times out at this barrier or a later one.
+typedef unsigned long long __attribute__((address_space(1))) gu64;
+typedef unsigned int __attribute__((address_space(1))) gu32;
+__device__ __forceinline__ bool grid_meet(unsigned* bar, unsigned* err, unsigned target, unsigned spin_limit,
+                                          int* s_abort, bool add = false, int* add_word = nullptr,
+                                          const int* add_count = nullptr) {
+    const int tid = threadIdx.x;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        if (add && *add_count)
+            __hip_atomic_fetch_add((gu32*)add_word, (unsigned)*add_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_fetch_add((gu32*)bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (tid < 64) {
+        unsigned spins = 0;
+        bool ok = true;
+        while (__hip_atomic_load((gu32*)bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
+            __builtin_amdgcn_s_sleep(1);
+            if (++spins > spin_limit) { ok = false; break; }
+        }
+        if (tid == 0 && !ok) {
+            *s_abort = 1;
+            __hip_atomic_store((gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    return *s_abort == 0;
+}
+
 struct QRArgs {
     double2* W;        // m x n column-major (ld = m), factorized in place: rows < k of a column hold R, column k's
                        //   rows > k keep x_k (v_k = (1; x_k * scale_k))
@@ -138,37 +252,14 @@ __global__ __launch_bounds__(256) void qr_step_kernel(QRArgs a, int k) {
     double* nout = a.norms + (size_t)((k + 1) & 1) * a.n;
     int p = k;
     if (a.pivot) {
-        double best = -1.0;
-        int bj = k;
-        for (int j = k + lane; j < a.n; j += 64) {
-            const double v = nin[pin[j]];
-            if (v > best) { best = v; bj = j; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ob = __shfl_xor(best, o);
-            const int oj = __shfl_xor(bj, o);
-            if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
-        }
-        p = bj;
-        double lim = a.tol2;
-        if (a.rel2 > 0.0) {
-            if (k == 0) {
-                lim = a.rel2 * best;
-                if (wave == 0 && lane == 0) *a.thr = lim;
-            } else {
-                lim = *a.thr;
-            }
-        }
-        if (best <= lim) {
+        const Pivot pv = pivot_search(k, a.n, lane, [&](int j) { return nin[pin[j]]; });
+        p = pv.j;
+        if (pv.best <= pivot_limit(k, a.tol2, a.rel2, pv.best, a.thr, wave == 0 && lane == 0)) {
             if (wave == 0 && lane == 0) a.ctrl[0] = k;
             return;
         }
     }
-    auto phys = [&](int j) {
-        if (!a.pivot) return j;
-        return j == k ? pin[p] : (j == p ? pin[k] : pin[j]);
-    };
+    auto phys = [&](int j) { return phys_col(a.pivot, pin, k, p, j); };
     const int pk = phys(k);
     const double2* x = a.W + (size_t)pk * a.m;
     double xn = 0.0;
@@ -190,31 +281,8 @@ __global__ __launch_bounds__(256) void qr_step_kernel(QRArgs a, int k) {
     const int j = k + 1 + wave;
     if (j >= a.n) return;
     const int c = phys(j);
-    double2* col = a.W + (size_t)c * a.m;
-    const double2 ck = col[k];
-    double2 s = c_zero();
-    for (int i = k + 1 + lane; i < a.m; i += 64) {
-        const double2 v = c_mul(x[i], R.scale);
-        const double2 ci = col[i];
-        s.x += v.x * ci.x + v.y * ci.y;
-        s.y += v.x * ci.y - v.y * ci.x;
-    }
-    s = wsum2(s);
-    s = c_add(s, ck);
-    const double2 ct = c_cmul(R.tau, s);  // conj(tau) * (v^H c)
-    double nn = 0.0;
-    for (int i = k + 1 + lane; i < a.m; i += 64) {
-        const double2 v = c_mul(x[i], R.scale);
-        double2 ci = col[i];
-        ci = c_sub(ci, c_mul(ct, v));
-        col[i] = ci;
-        nn += c_abs2(ci);
-    }
-    if (lane == 0) col[k] = c_sub(ck, ct);
-    if (a.pivot) {
-        nn = wsum(nn);
-        if (lane == 0) nout[c] = nn;
-    }
+    const double nn = apply_refl_wave(x, R.scale, R.tau, true, a.W + (size_t)c * a.m, k, a.m, lane, a.pivot);
+    if (a.pivot && lane == 0) nout[c] = nn;
 }
 
 // two reflectors per launch (plain QR only): every wave makes reflector k from column k, applies it to column k+1
@@ -339,21 +407,7 @@ __global__ __launch_bounds__(256) void qf_apply_kernel(QRArgs a, int rank, const
     double2* col = Q + (size_t)j * a.m;
     for (int i = min(j, i1 - 1); i >= i0; --i) {
         const int pc = a.pivot ? perm_final[i] : i;
-        const double2* x = a.X + (size_t)pc * a.m;
-        const double2 sc = a.scale[i], tau = a.tau[i];
-        const double2 ci0 = col[i];
-        double2 s = c_zero();
-        for (int r = i + 1 + lane; r < a.m; r += 64) {
-            const double2 v = c_mul(x[r], sc);
-            const double2 cr = col[r];
-            s.x += v.x * cr.x + v.y * cr.y;
-            s.y += v.x * cr.y - v.y * cr.x;
-        }
-        s = wsum2(s);
-        s = c_add(s, ci0);
-        const double2 t = c_mul(tau, s);
-        for (int r = i + 1 + lane; r < a.m; r += 64) col[r] = c_sub(col[r], c_mul(t, c_mul(x[r], sc)));
-        if (lane == 0) col[i] = c_sub(ci0, t);
+        apply_refl_wave(a.X + (size_t)pc * a.m, a.scale[i], a.tau[i], false, col, i, a.m, lane);
     }
 }
 
@@ -494,40 +548,17 @@ __global__ __launch_bounds__(WG_T) void qr_step_wg_kernel(QRArgs a, int k) {
     int p = k;
     if (a.pivot) {
         if (tid < 64) {
-            double best = -1.0;
-            int bj = k;
-            for (int jj = k + tid; jj < a.n; jj += 64) {
-                const double v = nin[pin[jj]];
-                if (v > best) { best = v; bj = jj; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ob = __shfl_xor(best, o);
-                const int oj = __shfl_xor(bj, o);
-                if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
-            }
-            if (tid == 0) { s_p = bj; s_best = best; }
+            const Pivot pv = pivot_search(k, a.n, tid, [&](int jj) { return nin[pin[jj]]; });
+            if (tid == 0) { s_p = pv.j; s_best = pv.best; }
         }
         __syncthreads();
         p = s_p;
-        double lim = a.tol2;
-        if (a.rel2 > 0.0) {
-            if (k == 0) {
-                lim = a.rel2 * s_best;
-                if (jw == 0 && tid == 0) *a.thr = lim;
-            } else {
-                lim = *a.thr;
-            }
-        }
-        if (s_best <= lim) {
+        if (s_best <= pivot_limit(k, a.tol2, a.rel2, s_best, a.thr, jw == 0 && tid == 0)) {
             if (jw == 0 && tid == 0) a.ctrl[0] = k;
             return;
         }
     }
-    auto phys = [&](int jj) {
-        if (!a.pivot) return jj;
-        return jj == k ? pin[p] : (jj == p ? pin[k] : pin[jj]);
-    };
+    auto phys = [&](int jj) { return phys_col(a.pivot, pin, k, p, jj); };
     const int j = k + jw;
     if (jw >= 1 && j >= a.n) return;
     const bool upd = jw >= 1;
@@ -786,23 +817,12 @@ __global__ __launch_bounds__(QS_THREADS) void qr_small_kernel(const double2* Win
         double* nout = s_norm[(k + 1) & 1];
         int p = k;
         if (pivot) {
-            double best = -1.0;
-            int bj = k;
-            for (int j = k + lane; j < n; j += 64) {
-                const double v = nin[pin[j]];
-                if (v > best) { best = v; bj = j; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ob = __shfl_xor(best, o);
-                const int oj = __shfl_xor(bj, o);
-                if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
-            }
-            if (k == 0 && rel2 > 0.0) tol2 = rel2 * best;  // relative mode: step 0 sees the largest column norm
-            if (best <= tol2) break;  // the same decision in every wave (same LDS values, same reduction)
-            p = bj;
+            const Pivot pv = pivot_search(k, n, lane, [&](int j) { return nin[pin[j]]; });
+            // the same decision in every wave (same LDS values, same reduction)
+            if (pv.best <= pivot_limit(k, tol2, rel2, pv.best, &tol2, true)) break;
+            p = pv.j;
         }
-        auto phys = [&](int j) { return j == k ? pin[p] : (j == p ? pin[k] : pin[j]); };
+        auto phys = [&](int j) { return phys_col(true, pin, k, p, j); };
         const double2* x = A + phys(k) * m;
         if constexpr (QE > 0) {
             // the pivot column in registers for the whole step; each trailing column: one round of LDS loads
@@ -868,6 +888,7 @@ __global__ __launch_bounds__(QS_THREADS) void qr_small_kernel(const double2* Win
                 if (lane == 0) { s_tau[k] = Rf.tau; s_scale[k] = Rf.scale; s_beta[k] = Rf.beta; }
                 for (int j = lane; j < n; j += 64) pout[j] = j < k ? pin[j] : phys(j);
             }
+            // apply_refl_wave's arithmetic written out: through the helper this instance takes 65 VGPRs, not 64
             const double2 sc = Rf.scale, tau = Rf.tau;
             for (int j = k + 1 + wave; j < n; j += nw) {
                 const int cidx = phys(j);
@@ -943,23 +964,8 @@ __global__ __launch_bounds__(QS_THREADS) void qr_small_kernel(const double2* Win
             }
         } else {
             for (int i = lane; i < m; i += 64) col[i] = make_double2(i == j ? 1.0 : 0.0, 0.0);
-            for (int i = j; i >= 0; --i) {
-                const double2* x = A + s_pf[i] * m;
-                const double2 sc = s_scale[i], tau = s_tau[i];
-                const double2 ci0 = col[i];
-                double2 sacc = c_zero();
-                for (int r = i + 1 + lane; r < m; r += 64) {
-                    const double2 v = c_mul(x[r], sc);
-                    const double2 cr = col[r];
-                    sacc.x += v.x * cr.x + v.y * cr.y;
-                    sacc.y += v.x * cr.y - v.y * cr.x;
-                }
-                sacc = wsum2(sacc);
-                sacc = c_add(sacc, ci0);
-                const double2 t = c_mul(tau, sacc);
-                for (int r = i + 1 + lane; r < m; r += 64) col[r] = c_sub(col[r], c_mul(t, c_mul(x[r], sc)));
-                if (lane == 0) col[i] = c_sub(ci0, t);
-            }
+            for (int i = j; i >= 0; --i)
+                apply_refl_wave(A + s_pf[i] * m, s_scale[i], s_tau[i], false, col, i, m, lane);
         }
     }
 }
@@ -1005,7 +1011,31 @@ __global__ void jac_init_kernel(double2* V, int n) {
     V[idx] = make_double2(i == j ? 1.0 : 0.0, 0.0);
 }
 
-// rotate the pair (p, q): [xp xq] J with J = [[cs, sn], [-sn e^{-i phi}, cs e^{-i phi}]], c = xp^H xq = |c| e^{i phi}
+// The rotation of a column pair (p, q) with a = |xp|^2, b = |xq|^2, c = xp^H xq = |c| e^{i phi}: [xp xq] J with
+// J = [[cs, sn], [-sn e^{-i phi}, cs e^{-i phi}]] makes the two columns orthogonal. rot = false: the pair is left alone.
+struct JacRot {
+    bool rot;
+    double2 eph;  // e^{-i phi}
+    double cs, sn;
+};
+__device__ __forceinline__ JacRot jac_angle(double a, double b, double2 c, double tol, double zero2) {
+    JacRot r{false, c_zero(), 1.0, 0.0};
+    const double ac = sqrt(c.x * c.x + c.y * c.y);
+    // a column at the rounding floor of the matrix (|x|^2 < zero2) holds no information: rotating it against the
+    // others only shrinks it by eps per pass towards the denormals, where its relative inner products stay noisy
+    // and the sweep would never end (LAPACK's zgesvj skips such columns the same way)
+    if (a < zero2 || b < zero2) return r;
+    if (!(ac > tol * sqrt(a * b)) || ac == 0.0) return r;
+    r.rot = true;
+    r.eph = make_double2(c.x / ac, -c.y / ac);
+    const double zeta = (b - a) / (2.0 * ac);
+    const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+    r.cs = 1.0 / sqrt(1.0 + t * t);
+    r.sn = r.cs * t;
+    return r;
+}
+
+// one wave rotates the pair of columns (xp, xq) in place and accumulates the rotation in (vp, vq); strided passes
 __device__ __forceinline__ bool jac_rotate(double2* xp, double2* xq, double2* vp, double2* vq, int len, int vlen,
                                            double tol, double zero2, int lane) {
     double a = 0.0, b = 0.0;
@@ -1020,28 +1050,22 @@ __device__ __forceinline__ bool jac_rotate(double2* xp, double2* xq, double2* vp
     a = wsum(a);
     b = wsum(b);
     c = wsum2(c);
-    const double ac = sqrt(c.x * c.x + c.y * c.y);
-    // a column at the rounding floor of the matrix (|x|^2 < zero2) holds no information: rotating it against the
-    // others only shrinks it by eps per pass towards the denormals, where its relative inner products stay noisy
-    // and the sweep would never end (LAPACK's zgesvj skips such columns the same way)
-    if (a < zero2 || b < zero2) return false;
-    if (!(ac > tol * sqrt(a * b)) || ac == 0.0) return false;
-    const double2 eph = make_double2(c.x / ac, -c.y / ac);  // e^{-i phi}
-    const double zeta = (b - a) / (2.0 * ac);
-    const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+    const JacRot J = jac_angle(a, b, c, tol, zero2);
+    if (!J.rot) return false;
+    const double cs = J.cs, sn = J.sn;
     for (int r = lane; r < len; r += 64) {
-        const double2 u = xp[r], w = c_mul(xq[r], eph);
+        const double2 u = xp[r], w = c_mul(xq[r], J.eph);
         xp[r] = make_double2(cs * u.x - sn * w.x, cs * u.y - sn * w.y);
         xq[r] = make_double2(sn * u.x + cs * w.x, sn * u.y + cs * w.y);
     }
     for (int r = lane; r < vlen; r += 64) {
-        const double2 u = vp[r], w = c_mul(vq[r], eph);
+        const double2 u = vp[r], w = c_mul(vq[r], J.eph);
         vp[r] = make_double2(cs * u.x - sn * w.x, cs * u.y - sn * w.y);
         vq[r] = make_double2(sn * u.x + cs * w.x, sn * u.y + cs * w.y);
     }
     return true;
 }
+
 
 __global__ __launch_bounds__(256) void jac_round_kernel(JacArgs a, int t) {
     const int lane = threadIdx.x & 63;
@@ -1103,9 +1127,7 @@ __global__ __launch_bounds__(QS_THREADS) void jac_small_kernel(double2* Xg, doub
 // count of a sweep goes to cnt[sweep] before the sweep's last arrive; every workgroup reads it after that barrier
 // and all leave together at the first sweep without a rotation. Needs all ceil(n/8) workgroups co-resident
 // (n <= 1024: at most 128 of 256 threads) and n <= 64 * EPL.
-typedef unsigned long long __attribute__((address_space(1))) gu64;
-typedef unsigned int __attribute__((address_space(1))) gu32;
-// 16-B element e of a buffer, sc1 (aux bit 16): coherent across the XCDs' L2s like the 8-B atomics above
+// 16-B element e of a buffer, sc1 (aux bit 16): coherent across the XCDs' L2s like the barrier's atomics
 typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ double2 ld16(__amdgpu_buffer_rsrc_t r, int e) {
     const v4u32 v = __builtin_amdgcn_raw_buffer_load_b128(r, e * 16, 0, 16);
@@ -1172,53 +1194,26 @@ __global__ __launch_bounds__(256) void jac_persist_kernel(JacArgs a, JacPersist 
                 sa = wsum(sa);
                 sb = wsum(sb);
                 c = wsum2(c);
-                const double ac = sqrt(c.x * c.x + c.y * c.y);
-                const bool rot = !(sa < zero2 || sb < zero2) && (ac > a.tol * sqrt(sa * sb)) && ac != 0.0;
-                if (rot) {
-                    const double2 eph = make_double2(c.x / ac, -c.y / ac);
-                    const double zeta = (sb - sa) / (2.0 * ac);
-                    const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                    const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
+                const JacRot J = jac_angle(sa, sb, c, a.tol, zero2);
+                if (J.rot) {
+                    const double cs = J.cs, sn = J.sn;
 #pragma unroll
                     for (int e = 0; e < EPL; ++e) {
                         const int r = lane + 64 * e;
                         if (r >= n) continue;
-                        const double2 u = up[e], w = c_mul(uq[e], eph);
+                        const double2 u = up[e], w = c_mul(uq[e], J.eph);
                         st16(rX, xo + r, make_double2(cs * u.x - sn * w.x, cs * u.y - sn * w.y));
                         st16(rX, yo + r, make_double2(sn * u.x + cs * w.x, sn * u.y + cs * w.y));
-                        const double2 u2 = wp[e], w2 = c_mul(wq[e], eph);
+                        const double2 u2 = wp[e], w2 = c_mul(wq[e], J.eph);
                         st16(rV, xo + r, make_double2(cs * u2.x - sn * w2.x, cs * u2.y - sn * w2.y));
                         st16(rV, yo + r, make_double2(sn * u2.x + cs * w2.x, sn * u2.y + cs * w2.y));
                     }
                     if (lane == 0) atomicAdd(&s_rot, 1);
                 }
             }
-            // ---- grid barrier (and, after a sweep's last round, the sweep's rotation count)
-            ++epoch;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                if (t == nn - 2 && s_rot)
-                    __hip_atomic_fetch_add((gu32*)(q.cnt + sweep), (unsigned)s_rot, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_fetch_add((gu32*)q.bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (tid < 64) {
-                const unsigned target = G * epoch;
-                unsigned spins = 0;
-                bool ok = true;
-                while (__hip_atomic_load((gu32*)q.bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > q.spin_limit) { ok = false; break; }
-                }
-                if (tid == 0 && !ok) {
-                    s_abort = 1;
-                    __hip_atomic_store((gu32*)q.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            __syncthreads();
-            if (s_abort) return;
+            // the grid barrier and, after a sweep's last round, the sweep's rotation count
+            if (!grid_meet(q.bar, q.err, G * ++epoch, q.spin_limit, &s_abort, t == nn - 2, q.cnt + sweep, &s_rot))
+                return;
         }
         if (tid == 0)
             s_done = __hip_atomic_load((gu32*)(q.cnt + sweep), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
@@ -1232,10 +1227,14 @@ __global__ __launch_bounds__(256) void jac_persist_kernel(JacArgs a, JacPersist 
 // round-robin tournament over the blocks each round, loads the pair's 2 JB columns of X and V into LDS (every load of
 // a wave in flight at once), runs one inner sweep over the 2 JB (2 JB - 1) / 2 local pairs (2 JB - 1 sub-rounds, one
 // wave per pair, each rotation on register copies of its four column slices), stores the columns back and meets the
-// grid at jac_persist_kernel's barrier (16-B sc1 accesses, one counter add per workgroup, bounded polls). A sweep is
+// grid at grid_meet (16-B sc1 accesses, one counter add per workgroup, bounded polls). A sweep is
 // ceil(n / JB) - 1 grid barriers instead of n - 1. Stops at the first sweep without a rotation. LDS 4 JB n complex.
 constexpr int JB = 4;
 
+// jac_rotate with the four column slices (LDS) in registers between the loads and the stores (n <= 64 EPL). Its body is
+// written out, jac_angle's rule included: one body over load / store functors shared with jac_persist_kernel moved
+// registers in both kernels, and through jac_angle jac_block_kernel's X, V and sigma came out with other last bits than
+// before (same instructions, same sweeps). A change to the rotation rule goes here and into jac_angle.
 template <int EPL>
 __device__ __forceinline__ bool jac_rotate_regs(double2* xp, double2* xq, double2* vp, double2* vq, int n, double tol,
                                                 double zero2, int lane) {
@@ -1365,32 +1364,10 @@ __global__ __launch_bounds__(256) void jac_block_kernel(JacArgs a, JacPersist q,
                     }
                 }
             }
-            // ---- grid barrier (and, after a sweep's last round, the sweep's rotation count)
-            ++epoch;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                if (t == nblk - 2 && s_rot)
-                    __hip_atomic_fetch_add((gu32*)(q.cnt + sweep), (unsigned)s_rot, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_fetch_add((gu32*)q.bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (tid < 64) {
-                const unsigned target = G * epoch;
-                unsigned spins = 0;
-                bool ok = true;
-                while (__hip_atomic_load((gu32*)q.bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > q.spin_limit) { ok = false; break; }
-                }
-                if (tid == 0 && !ok) {
-                    s_abort = 1;
-                    __hip_atomic_store((gu32*)q.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            __syncthreads();
-            if (s_abort) return;
+            // the grid barrier and, after a sweep's last round, the sweep's rotation count
+            if (!grid_meet(q.bar, q.err, G * ++epoch, q.spin_limit, &s_abort, t == nblk - 2, q.cnt + sweep,
+                           &s_rot))
+                return;
         }
         if (tid == 0)
             s_done = __hip_atomic_load((gu32*)(q.cnt + sweep), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
@@ -1406,7 +1383,7 @@ __global__ __launch_bounds__(256) void jac_block_kernel(JacArgs a, JacPersist q,
 // workgroup makes the same swap). Step k: the pivot search over the trailing norms (sc1 loads, the same scan and tie
 // rule as the launch path), the stop test, the swap; the pivot column's owner records the reflector, the trailing
 // workgroups read the pivot column (16-B sc1 loads), update their column in registers, store its rows >= k (sc1,
-// for a later pivot read and for R) and its trailing norm, then the grid meets at jac_persist_kernel's barrier.
+// for a later pivot read and for R) and its trailing norm, then the grid meets (grid_meet).
 // Workgroups whose column is eliminated only keep the barrier count. Results equal the launch path's bit for bit.
 // Needs all n workgroups co-resident (the host checks the occupancy; a timed-out barrier wait sets *q.err and every
 // workgroup leaves, and the host reruns the factorization one launch per step from a saved copy).
@@ -1434,7 +1411,7 @@ __global__ __launch_bounds__(WG_T) void qrcp_persist_kernel(QRArgs a, QRPersist 
         cj[e] = i < m ? a.W[(size_t)g * m + i] : c_zero();
     }
     bool done = false;  // this column is a reflector column (eliminated)
-    double lim = a.tol2;
+    double tol2 = a.tol2;
     int k = 0;
     unsigned epoch = 0;
     __syncthreads();
@@ -1442,31 +1419,20 @@ __global__ __launch_bounds__(WG_T) void qrcp_persist_kernel(QRArgs a, QRPersist 
         const double* nin = a.norms + (size_t)(k & 1) * n;
         double* nout = a.norms + (size_t)((k + 1) & 1) * n;
         if (a.pivot && tid < 64) {
-            double best = -1.0;
-            int bj = k;
-            for (int jj = k + tid; jj < n; jj += 64) {
+            const Pivot pv = pivot_search(k, n, tid, [&](int jj) {  // norms stored by other workgroups in this launch
                 const unsigned long long b = __hip_atomic_load((gu64*)(nin + s_perm[jj]), __ATOMIC_RELAXED,
                                                                __HIP_MEMORY_SCOPE_AGENT);
-                const double v = __longlong_as_double((long long)b);
-                if (v > best) { best = v; bj = jj; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ob = __shfl_xor(best, o);
-                const int oj = __shfl_xor(bj, o);
-                if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
-            }
-            if (tid == 0) { s_p = bj; s_best = best; }
+                return __longlong_as_double((long long)b);
+            });
+            if (tid == 0) { s_p = pv.j; s_best = pv.best; }
         }
         __syncthreads();
         const int p = a.pivot ? s_p : k;  // plain QR: no search, no stop (s_perm stays the identity)
         if (a.pivot) {
             const double sb = s_best;
-            if (a.rel2 > 0.0 && k == 0) {
-                lim = a.rel2 * sb;
-                if (g == 0 && tid == 0) *a.thr = lim;
-            }
-            if (sb <= lim) {
+            // step 0 makes the threshold (and leaves it in *a.thr, as the launch path does); a register keeps it
+            if (k == 0) tol2 = pivot_limit(0, tol2, a.rel2, sb, a.thr, g == 0 && tid == 0);
+            if (sb <= tol2) {
                 if (g == 0 && tid == 0) a.ctrl[0] = k;
                 break;
             }
@@ -1531,29 +1497,7 @@ __global__ __launch_bounds__(WG_T) void qrcp_persist_kernel(QRArgs a, QRPersist 
                 }
             }
         }
-        // ---- grid barrier
-        ++epoch;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add((gu32*)q.bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (tid < 64) {
-            const unsigned target = G * epoch;
-            unsigned spins = 0;
-            bool ok = true;
-            while (__hip_atomic_load((gu32*)q.bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > q.spin_limit) { ok = false; break; }
-            }
-            if (tid == 0 && !ok) {
-                s_abort = 1;
-                __hip_atomic_store((gu32*)q.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        __syncthreads();
-        if (s_abort) return;
+        if (!grid_meet(q.bar, q.err, G * ++epoch, q.spin_limit, &s_abort)) return;
     }
     // the final permutation where the launch path leaves it (the buffer of parity rank & 1)
     if (g == 0)
@@ -1651,34 +1595,84 @@ int cur_dev() {
     int d = 0;
     return hipGetDevice(&d) == hipSuccess && d >= 0 && d < 64 ? d : 0;
 }
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-unsigned long long g_attr_done = 0;  // bit d: the attributes are set on device d
-hipError_t small_attrs() {
+// set() once per device; done: bit d = done on device d
+template <class F>
+hipError_t once_per_device(unsigned long long& done, F&& set) {
     const int dev = cur_dev();
-    if (g_attr_done >> dev & 1ull) return hipSuccess;
-    const int lds = QS_MAX * (int)sizeof(double2);
-    hipError_t e = hipSuccess;
-    for (const void* f : {(const void*)qr_small_kernel<0>, (const void*)qr_small_kernel<1>,
-                          (const void*)qr_small_kernel<2>, (const void*)qr_small_kernel<4>,
-                          (const void*)qr_small_kernel<8>}) {
-        e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-    }
-    e = hipFuncSetAttribute((const void*)jac_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    g_attr_done |= 1ull << dev;
-    return hipSuccess;
+    if (done >> dev & 1ull) return hipSuccess;
+    const hipError_t e = set();
+    if (e == hipSuccess) done |= 1ull << dev;
+    return e;
 }
 
-// PQD_PTG_SMALL=0: every factorization on the multi-workgroup kernels (A/B and tests of both paths)
-bool small_ok() {
-    const char* e = getenv("PQD_PTG_SMALL");
-    return !(e && atoi(e) == 0);
+// Kernel instances are chosen on the host by a template constant (rows or elements per thread): f is a generic lambda
+// and gets std::integral_constant<int, V> for the listed V equal to v, or for the last one listed when none is (each
+// call site's fallback instance, as its hand-written switch had it).
+template <int V0, int... Vs, class F>
+decltype(auto) dispatch_pow2(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) {
+        return f(std::integral_constant<int, V0>{});
+    } else {
+        if (v == V0) return f(std::integral_constant<int, V0>{});
+        return dispatch_pow2<Vs...>(v, std::forward<F>(f));
+    }
 }
-int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return (e && *e) ? atoi(e) : dflt;
+#define KV(E) decltype(E)::value  // the constant a dispatch_pow2 lambda was called with
+
+// Every PQD_PTG_* switch the two entry points read (A/B runs and tests; INTEGRATION.md "Runtime switches", in that
+// order, then the timing-only PQD_PTG_DIAG). read_ptg_env() is the only place this file reads the environment. It runs once per
+// pqd_ptg_qr / pqd_ptg_jacobi call and its result is never kept: the tests flip switches between calls of one process.
+struct PtgEnv {
+    bool small;
+    int wg, pair, blocked, qfb, jpersist, jblock, qpersist, diag;
+    unsigned jspin, qspin;
+};
+PtgEnv read_ptg_env() {
+    auto raw = [](const char* name) { return getenv(name); };
+    // an empty value counts as unset
+    auto num = [&](const char* name, int unset) { const char* e = raw(name); return (e && *e) ? atoi(e) : unset; };
+    PtgEnv v;
+    const char* sm = raw("PQD_PTG_SMALL");
+    v.small = !(sm && atoi(sm) == 0);            // 0: every factorization on the multi-workgroup kernels (any set value that reads as 0)
+    v.wg = num("PQD_PTG_WG", 1);                  // 0: wave-per-column step kernels
+    v.pair = num("PQD_PTG_PAIR", 1);              // 0: one reflector per launch on plain QRs
+    v.blocked = num("PQD_PTG_BLOCKED", -1);       // blocked factorization of plain QRs: 1 always, 0 never, -1 by size
+    v.qfb = num("PQD_PTG_QFB", 1);                // 0: Q from the per-wave reflector kernel, not blocks of 32 reflectors
+    v.jpersist = num("PQD_PTG_JPERSIST", 1);      // 0: one Jacobi launch per round
+    v.jblock = num("PQD_PTG_JBLOCK", 1);          // 0: persistent Jacobi over single column pairs, not 4-column blocks
+    v.jspin = (unsigned)num("PQD_PTG_JSPIN", 1 << 22);  // polls per barrier wait of the persistent Jacobi (tests: 1)
+    v.qpersist = num("PQD_PTG_QPERSIST", 0);      // 1: pivoted QRs in one persistent launch, 2: plain QRs too
+    v.qspin = (unsigned)num("PQD_PTG_QSPIN", 1 << 22);  // polls per barrier wait of the persistent QR (tests: 1)
+    v.diag = num("PQD_PTG_DIAG", 0);              // single-workgroup QR, timing only: 1 no Q, 2 no column steps
+    return v;
+}
+
+constexpr int JB_LDS_MAX = 160 * 1024 - 256;  // jac_block_kernel's dynamic LDS; its own static words come on top
+unsigned long long g_small_attr = 0, g_jblock_attr = 0;
+hipError_t small_attrs() {
+    return once_per_device(g_small_attr, [] {
+        const int lds = QS_MAX * (int)sizeof(double2);
+        for (int qe : {0, 1, 2, 4, 8}) {
+            const hipError_t e = dispatch_pow2<1, 2, 4, 8, 0>(qe, [&](auto E) {
+                return hipFuncSetAttribute((const void*)qr_small_kernel<KV(E)>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            });
+            if (e != hipSuccess) return e;
+        }
+        return hipFuncSetAttribute((const void*)jac_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    });
+}
+hipError_t jac_block_attrs() {
+    return once_per_device(g_jblock_attr, [] {
+        for (int epl : {1, 2, 4, 8}) {
+            const hipError_t e = dispatch_pow2<1, 2, 4, 8>(epl, [&](auto E) {
+                return hipFuncSetAttribute((const void*)jac_block_kernel<KV(E)>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, JB_LDS_MAX);
+            });
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    });
 }
 
 // registers per thread of the workgroup-per-column kernels: the smallest EPT with 256 * EPT >= m (0: too tall)
@@ -1687,35 +1681,8 @@ int wg_ept(int m) {
         if (WG_T * e >= m) return e;
     return 0;
 }
-void launch_step2_wg(int ept, const QRArgs& a, int k, int grid, hipStream_t s) {
-    switch (ept) {
-        case 1: hipLaunchKernelGGL(qr_step2_wg_kernel<1>, dim3(grid), dim3(WG_T), 0, s, a, k); break;
-        case 2: hipLaunchKernelGGL(qr_step2_wg_kernel<2>, dim3(grid), dim3(WG_T), 0, s, a, k); break;
-        case 4: hipLaunchKernelGGL(qr_step2_wg_kernel<4>, dim3(grid), dim3(WG_T), 0, s, a, k); break;
-        case 8: hipLaunchKernelGGL(qr_step2_wg_kernel<8>, dim3(grid), dim3(WG_T), 0, s, a, k); break;
-        default: hipLaunchKernelGGL(qr_step2_wg_kernel<16>, dim3(grid), dim3(WG_T), 0, s, a, k); break;
-    }
-}
-void launch_step_wg(int ept, const QRArgs& a, int k, int grid, hipStream_t s) {
-    switch (ept) {
-        case 1: hipLaunchKernelGGL(qr_step_wg_kernel<1>, dim3(grid), dim3(WG_T), 0, s, a, k); break;
-        case 2: hipLaunchKernelGGL(qr_step_wg_kernel<2>, dim3(grid), dim3(WG_T), 0, s, a, k); break;
-        case 4: hipLaunchKernelGGL(qr_step_wg_kernel<4>, dim3(grid), dim3(WG_T), 0, s, a, k); break;
-        case 8: hipLaunchKernelGGL(qr_step_wg_kernel<8>, dim3(grid), dim3(WG_T), 0, s, a, k); break;
-        default: hipLaunchKernelGGL(qr_step_wg_kernel<16>, dim3(grid), dim3(WG_T), 0, s, a, k); break;
-    }
-}
 
-// the persistent QRCP kernel for ept, and whether its n workgroups (256 threads, n ints of LDS) can all be resident
-const void* qrcp_persist_fn(int ept) {
-    switch (ept) {
-        case 1: return (const void*)qrcp_persist_kernel<1>;
-        case 2: return (const void*)qrcp_persist_kernel<2>;
-        case 4: return (const void*)qrcp_persist_kernel<4>;
-        case 8: return (const void*)qrcp_persist_kernel<8>;
-        default: return (const void*)qrcp_persist_kernel<16>;
-    }
-}
+// whether the persistent QR kernel's n workgroups (256 threads, n ints of LDS) can all be resident
 bool qrcp_persist_fits(int ept, int n) {
     static int cus_d[64] = {0};
     static int per_cu_d[64][17] = {{0}};
@@ -1729,9 +1696,11 @@ bool qrcp_persist_fits(int ept, int n) {
     if (!per_cu[ept]) {
         int nb = 0;
         // LDS: the permutation (n ints) at the largest n taken (4096), so the answer holds for every n below it
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, qrcp_persist_fn(ept), WG_T, 4096 * sizeof(int)) !=
-            hipSuccess)
-            return false;
+        const hipError_t e = dispatch_pow2<1, 2, 4, 8, 16>(ept, [&](auto E) {
+            return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)qrcp_persist_kernel<KV(E)>, WG_T,
+                                                                4096 * sizeof(int));
+        });
+        if (e != hipSuccess) return false;
         per_cu[ept] = nb > 0 ? nb : -1;
     }
     return n <= 4096 && per_cu[ept] > 0 && (long long)per_cu[ept] * cus >= n;
@@ -1744,7 +1713,9 @@ void column_steps(const QRArgs& a, int k, int k_end, bool pairs, int ept, hipStr
     while (k < k_end) {
         if (pairs && k + 1 < k_end) {
             if (ept) {
-                launch_step2_wg(ept, a, k, std::max(2, a.n - k), s);
+                dispatch_pow2<1, 2, 4, 8, 16>(ept, [&](auto E) {
+                    hipLaunchKernelGGL(qr_step2_wg_kernel<KV(E)>, dim3(std::max(2, a.n - k)), dim3(WG_T), 0, s, a, k);
+                });
             } else {
                 const int nw = 2 + std::max(0, a.n - k - 2);
                 hipLaunchKernelGGL(qr_step2_kernel, dim3((nw + wpb - 1) / wpb), dim3(64 * wpb), 0, s, a, k);
@@ -1752,7 +1723,9 @@ void column_steps(const QRArgs& a, int k, int k_end, bool pairs, int ept, hipStr
             k += 2;
         } else {
             if (ept) {
-                launch_step_wg(ept, a, k, std::max(1, a.n - k), s);
+                dispatch_pow2<1, 2, 4, 8, 16>(ept, [&](auto E) {
+                    hipLaunchKernelGGL(qr_step_wg_kernel<KV(E)>, dim3(std::max(1, a.n - k)), dim3(WG_T), 0, s, a, k);
+                });
             } else {
                 const int nw = std::max(1, a.n - k - 1);
                 hipLaunchKernelGGL(qr_step_kernel, dim3((nw + wpb - 1) / wpb), dim3(64 * wpb), 0, s, a, k);
@@ -1767,20 +1740,6 @@ constexpr int QB = VHA_NB;
 struct BlockBufs {
     double2 *Vc, *S, *T, *Yp, *Zt;
 };
-size_t block_bytes(int m, int n) {
-    const size_t nch = (size_t)(m + VHA_RC - 1) / VHA_RC;
-    return al((size_t)QB * m * 16) + 2 * al((size_t)QB * QB * 16) + al(nch * n * QB * 16) + al((size_t)n * QB * 16);
-}
-BlockBufs carve_block(char*& c, int m, int n) {
-    BlockBufs b;
-    const size_t nch = (size_t)(m + VHA_RC - 1) / VHA_RC;
-    b.Vc = reinterpret_cast<double2*>(c); c += al((size_t)QB * m * 16);
-    b.S = reinterpret_cast<double2*>(c); c += al((size_t)QB * QB * 16);
-    b.T = reinterpret_cast<double2*>(c); c += al((size_t)QB * QB * 16);
-    b.Yp = reinterpret_cast<double2*>(c); c += al(nch * n * QB * 16);
-    b.Zt = reinterpret_cast<double2*>(c); c += al((size_t)n * QB * 16);
-    return b;
-}
 
 // V and S = V^H V (strict upper part) of reflectors i0 .. i0+nb-1 (X columns perm[i], perm == nullptr: i)
 void block_vt(const QRArgs& a, const int* perm, int i0, int nb, const BlockBufs& b, hipStream_t s) {
@@ -1803,12 +1762,144 @@ void block_apply(double2* A0, int lda, int ncol, int mm, int i0, int nb, int her
     hipLaunchKernelGGL(rank_update_kernel, dim3((mm + 255) / 256, ncol), dim3(256), 0, s, A0, lda, mm, b.Vc, nb, b.Zt);
 }
 
+// ---- pqd_ptg_qr in stages: the path, the scratch, one function per path, then R and Q -------------------------
+struct QrPath {
+    bool small;     // the single-workgroup kernel (the matrix fits in LDS)
+    int ept;        // > 0: workgroup-per-column step kernels with this many rows per thread; 0: wave per column
+    bool qpersist;  // every step in one persistent launch
+    bool pairs;     // two reflectors per launch (plain QRs)
+    bool blocked;   // panels of QB columns, compact-WY trailing update (plain QRs)
+    bool qfb;       // Q from blocks of QB reflectors
+    bool sepx;      // reflector columns in their own buffer X
+};
+QrPath choose_qr_path(const PtgEnv& env, int m, int n, int pivot) {
+    const int kmax = std::min(m, n);
+    QrPath p;
+    p.small = env.small && (size_t)m * n <= (size_t)QS_MAX && n <= 256;
+    p.ept = env.wg ? wg_ept(m) : 0;
+    // QRs whose columns fit in registers: every step in one persistent launch (PQD_PTG_QPERSIST=1: pivoted QRs, 2:
+    // pivoted and plain QRs; default 0: one launch per step). A plain QR then takes one reflector per step (no pairs).
+    // Measured slower than the launches (profiles/r04/ptgen/qpersist/: QRCP phases +8-13%, plain QRs +40%): each step
+    // is three dependent coherent round trips (the norm scan, the barrier, the pivot column), where back-to-back
+    // launches read the same data from L2
+    p.qpersist = !p.small && p.ept > 0 && kmax >= 2 &&
+                 (pivot ? env.qpersist >= 1 : (env.qpersist >= 2 && env.blocked != 1)) && qrcp_persist_fits(p.ept, n);
+    p.pairs = !pivot && !p.small && !p.qpersist && kmax >= 2 && env.pair != 0;
+    // blocked factorization: PQD_PTG_BLOCKED=1 always, 0 never, default from 10^6 elements (the size where the
+    // per-step trailing traffic of the column kernels starts to exceed the panels' extra launches; profiles/r04/ptgen)
+    p.blocked = !pivot && !p.small && !p.qpersist && m >= n && n > QB &&
+                (env.blocked == 1 || (env.blocked < 0 && (size_t)m * n >= (size_t)1000000));
+    p.qfb = !p.small && env.qfb != 0;
+    p.sepx = p.pairs || p.blocked;
+    return p;
+}
+
+// words of QRArgs.ctrl (ints)
+constexpr int QC_RANK = 0;         // the rank: kmax until a pivot step finds the trailing block below the tolerance
+constexpr int QC_SMALL_RANK = 8;   // the single-workgroup kernel's rank
+constexpr int QC_THR = 16;         // relative mode: the stop threshold (a double)
+constexpr int QC_BAR = 32;         // persistent kernel: barrier arrivals
+constexpr int QC_ERR = 40;         // persistent kernel: 1 after a barrier wait timed out
+constexpr int QC_PERSIST_WORDS = 16;  // from QC_BAR: zeroed before a persistent launch
+constexpr int QC_WORDS = 64;
+
+int qr_run_small(const QRArgs& a, const PtgEnv& env, bool unperm, double2* Q, double2* R, int32_t* perm_out,
+                 int32_t* rank_out, hipStream_t s) {
+    PCHK(small_attrs());
+    const int m = a.m, n = a.n;
+    const size_t lds = (size_t)m * n * sizeof(double2);
+    int* d_rank = a.ctrl + QC_SMALL_RANK;
+    const int qe = m <= 64 ? 1 : m <= 128 ? 2 : m <= 256 ? 4 : m <= 512 ? 8 : 0;
+    dispatch_pow2<1, 2, 4, 8, 0>(qe, [&](auto E) {
+        hipLaunchKernelGGL(qr_small_kernel<KV(E)>, dim3(1), dim3(QS_THREADS), lds, s, a.W, m, n, a.pivot, a.tol2, a.rel2,
+                           Q, R, perm_out, d_rank, unperm ? 1 : 0, env.diag);
+    });
+    PCHK(hipGetLastError());
+    if (!a.pivot) {  // the rank of a plain QR is min(m, n): no host round trip, the caller's work stays queued
+        *rank_out = a.kmax;
+        return PQD_OK;
+    }
+    int rank = 0;
+    PCHK(hipMemcpyAsync(&rank, d_rank, sizeof(int), hipMemcpyDeviceToHost, s));
+    PCHK(hipStreamSynchronize(s));
+    *rank_out = rank;
+    return PQD_OK;
+}
+
+void qr_init(const QRArgs& a, hipStream_t s) {
+    const int wpb = 4;
+    hipLaunchKernelGGL(qr_init_kernel, dim3((a.n + wpb - 1) / wpb), dim3(64 * wpb), 0, s, a);
+}
+
+void qr_run_blocked(const QRArgs& a, int ept, const BlockBufs& bb, hipStream_t s) {
+    for (int k0 = 0; k0 < a.kmax; k0 += QB) {
+        const int nb = std::min(QB, a.kmax - k0);
+        QRArgs ap = a;
+        ap.n = k0 + nb;  // the panel's column steps update the panel only
+        column_steps(ap, k0, k0 + nb, true, ept, s);
+        if (k0 + nb < a.n) {
+            block_vt(a, nullptr, k0, nb, bb, s);
+            block_apply(a.W + (size_t)(k0 + nb) * a.m + k0, a.m, a.n - k0 - nb, a.m - k0, k0, nb, 1, a.tau, bb, s);
+        }
+    }
+}
+
+// every step in one launch; a barrier wait that timed out (every workgroup has left) starts the factorization over
+// from the copy Wbak, one launch per step
+int qr_run_persistent(const QRArgs& a, int ept, const PtgEnv& env, double2* Wbak, hipStream_t s) {
+    const size_t wbytes = (size_t)a.m * a.n * sizeof(double2);
+    QRPersist q;
+    q.bar = reinterpret_cast<unsigned*>(a.ctrl + QC_BAR);
+    q.err = reinterpret_cast<unsigned*>(a.ctrl + QC_ERR);
+    q.spin_limit = env.qspin;
+    PCHK(hipMemsetAsync(a.ctrl + QC_BAR, 0, QC_PERSIST_WORDS * sizeof(int), s));
+    PCHK(hipMemcpyAsync(Wbak, a.W, wbytes, hipMemcpyDeviceToDevice, s));
+    dispatch_pow2<1, 2, 4, 8, 16>(ept, [&](auto E) {
+        hipLaunchKernelGGL(qrcp_persist_kernel<KV(E)>, dim3(a.n), dim3(WG_T), (size_t)a.n * sizeof(int), s, a, q);
+    });
+    PCHK(hipGetLastError());
+    unsigned e = 0;
+    PCHK(hipMemcpyAsync(&e, q.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    PCHK(hipStreamSynchronize(s));
+    if (e) {
+        PCHK(hipMemcpyAsync(a.W, Wbak, wbytes, hipMemcpyDeviceToDevice, s));
+        qr_init(a, s);
+        column_steps(a, 0, a.kmax, false, ept, s);
+        g_qr_fallbacks.fetch_add(1);
+    }
+    return PQD_OK;
+}
+
+// R (rank x n) and the permutation, then Q = H_0 ... H_{rank-1} [I; 0]
+void qr_extract_form_q(const QRArgs& a, int rank, bool unperm, bool qfb, const BlockBufs& bb, double2* Q, double2* R,
+                       int32_t* perm_out, hipStream_t s) {
+    const int m = a.m, n = a.n, wpb = 4;
+    const int tot = std::max(rank * n, n);
+    hipLaunchKernelGGL(qr_extract_r_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, a, rank, R, perm_out,
+                       unperm ? 1 : 0);
+    if (rank <= 0) return;
+    const size_t mq = (size_t)m * rank;
+    hipLaunchKernelGGL(qf_init_kernel, dim3((unsigned)((mq + 255) / 256)), dim3(256), 0, s, Q, m, rank);
+    if (qfb && rank > 2 * QB) {
+        // blocks of QB reflectors from the last: Q[i0:, i0:] <- (I - V T V^H) Q[i0:, i0:]
+        const int* pf = a.pivot ? perm_out : nullptr;
+        for (int i0 = ((rank - 1) / QB) * QB; i0 >= 0; i0 -= QB) {
+            const int nb = std::min(QB, rank - i0);
+            block_vt(a, pf, i0, nb, bb, s);
+            block_apply(Q + (size_t)i0 * m + i0, m, rank - i0, m - i0, i0, nb, 0, a.tau, bb, s);
+        }
+    } else {
+        for (int i1 = rank; i1 > 0; i1 -= QF_RB) {
+            const int i0 = std::max(0, i1 - QF_RB);
+            const int ncol = rank - i0;
+            hipLaunchKernelGGL(qf_apply_kernel, dim3((ncol + wpb - 1) / wpb), dim3(64 * wpb), 0, s, a, rank, perm_out, Q,
+                               i0, i1);
+        }
+    }
+}
+
 }  // namespace
 
-// Switches (read per call, for A/B runs and tests): PQD_PTG_SMALL=0 (no single-workgroup kernel), PQD_PTG_WG=0 (wave-
-// per-column step kernels), PQD_PTG_PAIR=0 (one reflector per launch), PQD_PTG_BLOCKED=1 (blocked factorization of
-// plain QRs: panels of 32 columns, trailing update V T^H V^H A), PQD_PTG_QFB=0 (Q from the per-wave reflector kernel
-// instead of blocks of 32 reflectors).
 extern "C" int pqd_ptg_qr(void* stream, pqd_c128* Wp, int32_t m, int32_t n, int32_t pivot, double tol,
                           pqd_c128* Qp, pqd_c128* Rp, int32_t* perm_out, int32_t* rank_out) {
     if (!Wp || !Qp || !Rp || !perm_out || !rank_out) return perr(PQD_ERR_ARG, "pqd_ptg_qr: NULL argument");
@@ -1819,148 +1910,61 @@ extern "C" int pqd_ptg_qr(void* stream, pqd_c128* Wp, int32_t m, int32_t n, int3
     double2* Q = reinterpret_cast<double2*>(Qp);
     double2* R = reinterpret_cast<double2*>(Rp);
     const int kmax = std::min(m, n);
-    // tol >= 0: absolute; tol < 0: relative to the largest column norm of W (found on the device, no host pass)
-    const double tol2 = pivot && tol >= 0.0 ? tol * tol : -1.0;
     const bool unperm = pivot == 2;  // R returned in the original column order (R P^T)
-    const double rel2 = pivot && tol < 0.0 ? tol * tol : 0.0;
-    void* base = nullptr;
-    const bool small = small_ok() && (size_t)m * n <= (size_t)QS_MAX && n <= 256;
-    const int ept = env_int("PQD_PTG_WG", 1) ? wg_ept(m) : 0;
-    // blocked factorization: PQD_PTG_BLOCKED=1 always, 0 never, default from 10^6 elements (the size where the
-    // per-step trailing traffic of the column kernels starts to exceed the panels' extra launches; profiles/r04/ptgen)
-    const int blk_env = env_int("PQD_PTG_BLOCKED", -1);
-    // QRs whose columns fit in registers: every step in one persistent launch (PQD_PTG_QPERSIST=1: pivoted QRs, 2:
-    // pivoted and plain QRs; default 0: one launch per step). A plain QR then takes one reflector per step (no pairs).
-    // Measured slower than the launches (profiles/r04/ptgen/qpersist/: QRCP phases +8-13%, plain QRs +40%): each step
-    // is three dependent coherent round trips (the norm scan, the barrier, the pivot column), where back-to-back
-    // launches read the same data from L2
-    const int qp_env = env_int("PQD_PTG_QPERSIST", 0);
-    const bool qpersist = !small && ept > 0 && kmax >= 2 && (pivot ? qp_env >= 1 : (qp_env >= 2 && blk_env != 1)) &&
-                          qrcp_persist_fits(ept, n);
-    const bool pairs = !pivot && !small && !qpersist && kmax >= 2 && env_int("PQD_PTG_PAIR", 1) != 0;
-    const bool blocked = !pivot && !small && !qpersist && m >= n && n > QB &&
-                         (blk_env == 1 || (blk_env < 0 && (size_t)m * n >= (size_t)1000000));
-    const bool qfb = !small && env_int("PQD_PTG_QFB", 1) != 0;
-    const bool sepx = pairs || blocked;  // reflector columns in their own buffer X
-    const size_t b_tau = al(kmax * sizeof(double2)), b_beta = al(kmax * sizeof(double)),
-                 b_perm = al(2 * (size_t)n * sizeof(int)), b_norm = al(2 * (size_t)n * sizeof(double)),
-                 b_ctrl = al(64 * sizeof(int)), b_x = sepx ? al((size_t)m * kmax * sizeof(double2)) : 0,
-                 b_blk = (blocked || qfb) ? block_bytes(m, n) : 0,
-                 b_bak = qpersist ? al((size_t)m * n * sizeof(double2)) : 0;
-    PCHK(scratch(s, 2 * b_tau + b_beta + b_perm + b_norm + b_ctrl + b_x + b_blk + b_bak, &base));
-    char* c = static_cast<char*>(base);
+    const PtgEnv env = read_ptg_env();
+    const QrPath path = choose_qr_path(env, m, n, pivot);
+
     QRArgs a;
-    a.W = W; a.m = m; a.n = n; a.kmax = kmax; a.pivot = pivot ? 1 : 0; a.tol2 = tol2; a.rel2 = rel2;
-    a.tau = reinterpret_cast<double2*>(c); c += b_tau;
-    a.scale = reinterpret_cast<double2*>(c); c += b_tau;
-    a.beta = reinterpret_cast<double*>(c); c += b_beta;
-    a.perm = reinterpret_cast<int*>(c); c += b_perm;
-    a.norms = reinterpret_cast<double*>(c); c += b_norm;
-    a.ctrl = reinterpret_cast<int*>(c); c += b_ctrl;
-    a.X = sepx ? reinterpret_cast<double2*>(c) : W;
-    c += b_x;
+    a.W = W; a.m = m; a.n = n; a.kmax = kmax; a.pivot = pivot ? 1 : 0;
+    // tol >= 0: absolute; tol < 0: relative to the largest column norm of W (found on the device, no host pass)
+    a.tol2 = pivot && tol >= 0.0 ? tol * tol : -1.0;
+    a.rel2 = pivot && tol < 0.0 ? tol * tol : 0.0;
     BlockBufs bb{};
-    if (b_blk) bb = carve_block(c, m, n);
-    double2* Wbak = b_bak ? reinterpret_cast<double2*>(c) : nullptr;  // after the blocks: carve_block advanced c
-    c += b_bak;
-    int* d_rank = a.ctrl + 8;
-    a.thr = reinterpret_cast<double*>(a.ctrl + 16);
-    if (small) {
-        PCHK(small_attrs());
-        const size_t lds = (size_t)m * n * sizeof(double2);
-        const int diag = env_int("PQD_PTG_DIAG", 0);
-        const int qe = m <= 64 ? 1 : m <= 128 ? 2 : m <= 256 ? 4 : m <= 512 ? 8 : 0;
-#define PQD_QS(QEV) hipLaunchKernelGGL(qr_small_kernel<QEV>, dim3(1), dim3(QS_THREADS), lds, s, W, m, n, a.pivot, \
-                                       tol2, rel2, Q, R, perm_out, d_rank, unperm ? 1 : 0, diag)
-        switch (qe) {
-            case 1: PQD_QS(1); break;
-            case 2: PQD_QS(2); break;
-            case 4: PQD_QS(4); break;
-            case 8: PQD_QS(8); break;
-            default: PQD_QS(0); break;
+    double2* Wbak = nullptr;
+    auto carve = [&](Carve& c) {
+        a.tau = c.take<double2>(kmax);
+        a.scale = c.take<double2>(kmax);
+        a.beta = c.take<double>(kmax);
+        a.perm = c.take<int>(2 * (size_t)n);
+        a.norms = c.take<double>(2 * (size_t)n);
+        a.ctrl = c.take<int>(QC_WORDS);
+        a.X = path.sepx ? c.take<double2>((size_t)m * kmax) : W;
+        if (path.blocked || path.qfb) {
+            const size_t nch = (size_t)(m + VHA_RC - 1) / VHA_RC;
+            bb.Vc = c.take<double2>((size_t)QB * m);
+            bb.S = c.take<double2>((size_t)QB * QB);
+            bb.T = c.take<double2>((size_t)QB * QB);
+            bb.Yp = c.take<double2>(nch * n * QB);
+            bb.Zt = c.take<double2>((size_t)n * QB);
         }
-#undef PQD_QS
-        PCHK(hipGetLastError());
-        if (!pivot) {  // the rank of a plain QR is min(m, n): no host round trip, the caller's work stays queued
-            *rank_out = kmax;
-            return PQD_OK;
-        }
-        int rank = 0;
-        PCHK(hipMemcpyAsync(&rank, d_rank, sizeof(int), hipMemcpyDeviceToHost, s));
-        PCHK(hipStreamSynchronize(s));
-        *rank_out = rank;
-        return PQD_OK;
-    }
-    const int wpb = 4;
-    hipLaunchKernelGGL(qr_init_kernel, dim3((n + wpb - 1) / wpb), dim3(64 * wpb), 0, s, a);
-    if (blocked) {
-        for (int k0 = 0; k0 < kmax; k0 += QB) {
-            const int nb = std::min(QB, kmax - k0);
-            QRArgs ap = a;
-            ap.n = k0 + nb;  // the panel's column steps update the panel only
-            column_steps(ap, k0, k0 + nb, true, ept, s);
-            if (k0 + nb < n) {
-                block_vt(a, nullptr, k0, nb, bb, s);
-                block_apply(W + (size_t)(k0 + nb) * m + k0, m, n - k0 - nb, m - k0, k0, nb, 1, a.tau, bb, s);
-            }
-        }
-    } else if (qpersist) {
-        QRPersist q;
-        q.bar = reinterpret_cast<unsigned*>(a.ctrl + 32);
-        q.err = reinterpret_cast<unsigned*>(a.ctrl + 40);
-        q.spin_limit = (unsigned)env_int("PQD_PTG_QSPIN", 1 << 22);  // polls per barrier wait (tests: 1)
-        PCHK(hipMemsetAsync(a.ctrl + 32, 0, 16 * sizeof(int), s));
-        PCHK(hipMemcpyAsync(Wbak, W, (size_t)m * n * sizeof(double2), hipMemcpyDeviceToDevice, s));
-        const size_t lds = (size_t)n * sizeof(int);
-        switch (ept) {
-            case 1: hipLaunchKernelGGL(qrcp_persist_kernel<1>, dim3(n), dim3(WG_T), lds, s, a, q); break;
-            case 2: hipLaunchKernelGGL(qrcp_persist_kernel<2>, dim3(n), dim3(WG_T), lds, s, a, q); break;
-            case 4: hipLaunchKernelGGL(qrcp_persist_kernel<4>, dim3(n), dim3(WG_T), lds, s, a, q); break;
-            case 8: hipLaunchKernelGGL(qrcp_persist_kernel<8>, dim3(n), dim3(WG_T), lds, s, a, q); break;
-            default: hipLaunchKernelGGL(qrcp_persist_kernel<16>, dim3(n), dim3(WG_T), lds, s, a, q); break;
-        }
-        PCHK(hipGetLastError());
-        unsigned e = 0;
-        PCHK(hipMemcpyAsync(&e, q.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        PCHK(hipStreamSynchronize(s));
-        if (e) {  // a barrier wait timed out: every workgroup has left; start over from the copy, one launch per step
-            PCHK(hipMemcpyAsync(W, Wbak, (size_t)m * n * sizeof(double2), hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL(qr_init_kernel, dim3((n + wpb - 1) / wpb), dim3(64 * wpb), 0, s, a);
-            column_steps(a, 0, kmax, false, ept, s);
-            g_qr_fallbacks.fetch_add(1);
-        }
+        if (path.qpersist) Wbak = c.take<double2>((size_t)m * n);
+    };
+    Carve sz;
+    carve(sz);
+    void* base = nullptr;
+    PCHK(scratch(s, sz.off, &base));
+    Carve cv;
+    cv.base = static_cast<char*>(base);
+    carve(cv);
+    a.thr = reinterpret_cast<double*>(a.ctrl + QC_THR);
+
+    if (path.small) return qr_run_small(a, env, unperm, Q, R, perm_out, rank_out, s);
+    qr_init(a, s);
+    if (path.blocked) {
+        qr_run_blocked(a, path.ept, bb, s);
+    } else if (path.qpersist) {
+        const int rc = qr_run_persistent(a, path.ept, env, Wbak, s);
+        if (rc) return rc;
     } else {
-        column_steps(a, 0, kmax, pairs, ept, s);
+        column_steps(a, 0, kmax, path.pairs, path.ept, s);
     }
     PCHK(hipGetLastError());
     int rank = kmax;
     if (pivot) {  // the stopping step decides the rank: one host round trip
-        PCHK(hipMemcpyAsync(&rank, a.ctrl, sizeof(int), hipMemcpyDeviceToHost, s));
+        PCHK(hipMemcpyAsync(&rank, a.ctrl + QC_RANK, sizeof(int), hipMemcpyDeviceToHost, s));
         PCHK(hipStreamSynchronize(s));
     }
-    const int tot = std::max(rank * n, n);
-    hipLaunchKernelGGL(qr_extract_r_kernel, dim3((tot + 255) / 256), dim3(256), 0, s, a, rank, R, perm_out,
-                       unperm ? 1 : 0);
-    if (rank > 0) {
-        const size_t mq = (size_t)m * rank;
-        hipLaunchKernelGGL(qf_init_kernel, dim3((unsigned)((mq + 255) / 256)), dim3(256), 0, s, Q, m, rank);
-        if (qfb && rank > 2 * QB) {
-            // Q = H_0 ... H_{rank-1} [I; 0], blocks of QB reflectors from the last: Q[i0:, i0:] <- (I - V T V^H) Q[i0:, i0:]
-            const int* pf = a.pivot ? perm_out : nullptr;
-            for (int i0 = ((rank - 1) / QB) * QB; i0 >= 0; i0 -= QB) {
-                const int nb = std::min(QB, rank - i0);
-                block_vt(a, pf, i0, nb, bb, s);
-                block_apply(Q + (size_t)i0 * m + i0, m, rank - i0, m - i0, i0, nb, 0, a.tau, bb, s);
-            }
-        } else {
-            for (int i1 = rank; i1 > 0; i1 -= QF_RB) {
-                const int i0 = std::max(0, i1 - QF_RB);
-                const int ncol = rank - i0;
-                hipLaunchKernelGGL(qf_apply_kernel, dim3((ncol + wpb - 1) / wpb), dim3(64 * wpb), 0, s, a, rank,
-                                   perm_out, Q, i0, i1);
-            }
-        }
-    }
+    qr_extract_form_q(a, rank, unperm, path.qfb, bb, Q, R, perm_out, s);
     PCHK(hipGetLastError());
     *rank_out = rank;
     return PQD_OK;
@@ -1978,6 +1982,91 @@ extern "C" int pqd_ptg_qr_counters(int32_t* qrcp_fallbacks) {
     return PQD_OK;
 }
 
+namespace {
+// ---- pqd_ptg_jacobi in stages ----------------------------------------------------------------------------------
+// words of the Jacobi counter block (ints)
+constexpr int JC_COUNT = 0;         // rotations of the sweep in flight (one launch per round); the small kernel's sweeps
+constexpr int JC_ZERO2 = 8;         // the zero-column threshold (a double)
+constexpr int JC_BAR = 16;          // persistent kernels: barrier arrivals
+constexpr int JC_ERR = 32;          // persistent kernels: 1 after a barrier wait timed out
+constexpr int JC_SWEEPS = 48;       // persistent kernels: sweeps done
+constexpr int JC_SWEEP_CNT = 64;    // persistent kernels: rotations of each sweep
+constexpr int JC_MAX_SWEEPS = 200;  // most sweeps a persistent launch can count
+constexpr int JC_WORDS = JC_SWEEP_CNT + JC_MAX_SWEEPS;
+
+void jac_init(double2* V, int n, hipStream_t s) {
+    const size_t nv = (size_t)n * n;
+    hipLaunchKernelGGL(jac_init_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, V, n);
+}
+
+// all sweeps in one launch of the block kernel (or of the column-pair kernel). done = false: a barrier wait timed out
+// (workgroups not co-resident, e.g. under contention from other work on the device), every workgroup has left and X,
+// V are as before the launch again, for the caller to run one launch per round
+int jac_run_persistent(const JacArgs& a, int epl, const PtgEnv& env, int* cnt, double2* Xbak, int max_sweeps,
+                       bool& done, int& sweeps, hipStream_t s) {
+    const int n = a.n, wpb = 4;
+    const size_t xbytes = (size_t)n * n * sizeof(double2);
+    PCHK(hipMemcpyAsync(Xbak, a.X, xbytes, hipMemcpyDeviceToDevice, s));
+    JacPersist q;
+    q.bar = reinterpret_cast<unsigned*>(cnt + JC_BAR);
+    q.err = reinterpret_cast<unsigned*>(cnt + JC_ERR);
+    q.sweeps = cnt + JC_SWEEPS;
+    q.cnt = cnt + JC_SWEEP_CNT;
+    q.max_sweeps = max_sweeps;
+    q.spin_limit = env.jspin;
+    PCHK(hipMemsetAsync(cnt + JC_BAR, 0, (JC_WORDS - JC_BAR) * sizeof(int), s));
+    const dim3 b(64 * wpb);
+    int nblk = (n + JB - 1) / JB;
+    nblk += nblk & 1;  // even: the round-robin pairs every block each round (a block past n is all dummies)
+    const size_t lds_blk = (size_t)4 * JB * n * sizeof(double2);
+    // PQD_PTG_JBLOCK=0: the column-pair kernel (one grid barrier per tournament round of single columns)
+    const bool jblock = env.jblock != 0 && epl <= 8 && lds_blk <= (size_t)JB_LDS_MAX && nblk >= 2;
+    if (jblock) {
+        PCHK(jac_block_attrs());
+        dispatch_pow2<1, 2, 4, 8>(epl, [&](auto E) {
+            hipLaunchKernelGGL(jac_block_kernel<KV(E)>, dim3(nblk / 2), b, lds_blk, s, a, q, nblk);
+        });
+    } else {
+        dispatch_pow2<1, 2, 4, 8, 16>(epl, [&](auto E) {
+            hipLaunchKernelGGL(jac_persist_kernel<KV(E)>, dim3((a.nn / 2 + wpb - 1) / wpb), b, 0, s, a, q);
+        });
+    }
+    PCHK(hipGetLastError());
+    int h[2] = {0, 0};
+    PCHK(hipMemcpyAsync(&h[0], q.sweeps, sizeof(int), hipMemcpyDeviceToHost, s));
+    PCHK(hipMemcpyAsync(&h[1], q.err, sizeof(int), hipMemcpyDeviceToHost, s));
+    PCHK(hipStreamSynchronize(s));
+    done = h[1] == 0;
+    if (done) {
+        sweeps = h[0];
+    } else {
+        PCHK(hipMemcpyAsync(a.X, Xbak, xbytes, hipMemcpyDeviceToDevice, s));
+        jac_init(a.V, n, s);
+        g_jac_fallbacks.fetch_add(1);
+    }
+    return PQD_OK;
+}
+
+// one launch per tournament round; the host stops at the first sweep without a rotation
+int jac_run_rounds(const JacArgs& a, int* cnt, int max_sweeps, int& sweeps, hipStream_t s) {
+    const int npair = a.nn / 2, wpb = 4;
+    bool conv = false;
+    for (; sweeps < max_sweeps;) {
+        PCHK(hipMemsetAsync(cnt + JC_COUNT, 0, sizeof(int), s));
+        for (int t = 0; t < a.nn - 1; ++t)
+            hipLaunchKernelGGL(jac_round_kernel, dim3((npair + wpb - 1) / wpb), dim3(64 * wpb), 0, s, a, t);
+        PCHK(hipGetLastError());
+        int h = 0;
+        PCHK(hipMemcpyAsync(&h, cnt + JC_COUNT, sizeof(int), hipMemcpyDeviceToHost, s));
+        PCHK(hipStreamSynchronize(s));
+        ++sweeps;
+        if (h == 0) { conv = true; break; }
+    }
+    if (!conv) sweeps = max_sweeps + 1;
+    return PQD_OK;
+}
+}  // namespace
+
 extern "C" int pqd_ptg_jacobi(void* stream, pqd_c128* Xp, int32_t n, pqd_c128* Vp, double* sigma, double tol,
                               double zero_tol, int32_t max_sweeps, int32_t* sweeps_out) {
     if (!Xp || !Vp || !sigma || !sweeps_out) return perr(PQD_ERR_ARG, "pqd_ptg_jacobi: NULL argument");
@@ -1986,101 +2075,45 @@ extern "C" int pqd_ptg_jacobi(void* stream, pqd_c128* Xp, int32_t n, pqd_c128* V
     hipStream_t s = (hipStream_t)stream;
     double2* X = reinterpret_cast<double2*>(Xp);
     double2* V = reinterpret_cast<double2*>(Vp);
+    const PtgEnv env = read_ptg_env();
+    // the counters, then room for a copy of X (a persistent launch that times out is rerun from it)
+    int* cnt = nullptr;
+    double2* Xbak = nullptr;
+    auto carve = [&](Carve& c) {
+        cnt = c.take<int>(JC_WORDS);
+        Xbak = c.take<double2>((size_t)n * n);
+    };
+    Carve sz;
+    carve(sz);
     void* base = nullptr;
-    // counters, then a copy of X: a persistent launch whose grid barrier times out (workgroups not co-resident, e.g.
-    // under contention from other work on the device) is rerun from this copy with one launch per round
-    const size_t b_cnt = al((64 + 200) * sizeof(int));
-    PCHK(scratch(s, b_cnt + al((size_t)n * n * sizeof(double2)), &base));
-    int* cnt = static_cast<int*>(base);
-    double2* Xbak = reinterpret_cast<double2*>(static_cast<char*>(base) + b_cnt);
-    double* zero2 = reinterpret_cast<double*>(cnt + 8);
+    PCHK(scratch(s, sz.off, &base));
+    Carve cv;
+    cv.base = static_cast<char*>(base);
+    carve(cv);
+    double* zero2 = reinterpret_cast<double*>(cnt + JC_ZERO2);
     int sweeps = 0;
     // zero threshold relative to the Frobenius norm (rotation-invariant): |x_j| < zero_tol * ||X||_F
     hipLaunchKernelGGL(jac_zero2_kernel, dim3(1), dim3(1024), 0, s, X, n, zero_tol * zero_tol, zero2);
-    if (small_ok() && 2 * (size_t)n * n <= (size_t)QS_MAX) {
+    if (env.small && 2 * (size_t)n * n <= (size_t)QS_MAX) {
         PCHK(small_attrs());
         hipLaunchKernelGGL(jac_small_kernel, dim3(1), dim3(QS_THREADS), 2 * (size_t)n * n * sizeof(double2), s, X, V,
-                           n, tol, zero2, max_sweeps, cnt);
+                           n, tol, zero2, max_sweeps, cnt + JC_COUNT);
         PCHK(hipGetLastError());
-        PCHK(hipMemcpyAsync(&sweeps, cnt, sizeof(int), hipMemcpyDeviceToHost, s));
+        PCHK(hipMemcpyAsync(&sweeps, cnt + JC_COUNT, sizeof(int), hipMemcpyDeviceToHost, s));
         PCHK(hipStreamSynchronize(s));
     } else {
         JacArgs a;
-        a.X = X; a.V = V; a.n = n; a.nn = n + (n & 1); a.tol = tol; a.zero2 = zero2; a.count = cnt;
-        const size_t nv = (size_t)n * n;
-        hipLaunchKernelGGL(jac_init_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, V, n);
-        const int npair = a.nn / 2, wpb = 4;
+        a.X = X; a.V = V; a.n = n; a.nn = n + (n & 1); a.tol = tol; a.zero2 = zero2; a.count = cnt + JC_COUNT;
+        jac_init(V, n, s);
         const int epl = n <= 64 ? 1 : n <= 128 ? 2 : n <= 256 ? 4 : n <= 512 ? 8 : n <= 1024 ? 16 : 0;
-        bool persist = epl && env_int("PQD_PTG_JPERSIST", 1) != 0 && max_sweeps <= 200;
-        if (persist) {
-            PCHK(hipMemcpyAsync(Xbak, X, nv * sizeof(double2), hipMemcpyDeviceToDevice, s));
-            JacPersist q;
-            q.bar = reinterpret_cast<unsigned*>(cnt + 16);
-            q.err = reinterpret_cast<unsigned*>(cnt + 32);
-            q.sweeps = cnt + 48;
-            q.cnt = cnt + 64;
-            q.max_sweeps = max_sweeps;
-            q.spin_limit = (unsigned)env_int("PQD_PTG_JSPIN", 1 << 22);  // polls per barrier wait (tests: 1)
-            PCHK(hipMemsetAsync(cnt + 16, 0, (64 + 200) * sizeof(int) - 16 * sizeof(int), s));
-            const dim3 g((npair + wpb - 1) / wpb), b(64 * wpb);
-            int nblk = (n + JB - 1) / JB;
-            nblk += nblk & 1;  // even: the round-robin pairs every block each round (a block past n is all dummies)
-            const size_t lds_blk = (size_t)4 * JB * n * sizeof(double2);
-            constexpr int JB_LDS_MAX = 160 * 1024 - 256;  // the kernel's own static LDS words come on top
-            // PQD_PTG_JBLOCK=0: the column-pair kernel (one grid barrier per tournament round of single columns)
-            const bool jblock = env_int("PQD_PTG_JBLOCK", 1) != 0 && epl <= 8 && lds_blk <= (size_t)JB_LDS_MAX &&
-                                nblk >= 2;
-            if (jblock) {
-                static unsigned long long attr = 0;  // bit d: set on device d
-                const int dev = cur_dev();
-                if (!(attr >> dev & 1ull)) {
-                    for (const void* f : {(const void*)jac_block_kernel<1>, (const void*)jac_block_kernel<2>,
-                                          (const void*)jac_block_kernel<4>, (const void*)jac_block_kernel<8>})
-                        PCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, JB_LDS_MAX));
-                    attr |= 1ull << dev;
-                }
-                const dim3 gb(nblk / 2);
-                switch (epl) {
-                    case 1: hipLaunchKernelGGL(jac_block_kernel<1>, gb, b, lds_blk, s, a, q, nblk); break;
-                    case 2: hipLaunchKernelGGL(jac_block_kernel<2>, gb, b, lds_blk, s, a, q, nblk); break;
-                    case 4: hipLaunchKernelGGL(jac_block_kernel<4>, gb, b, lds_blk, s, a, q, nblk); break;
-                    default: hipLaunchKernelGGL(jac_block_kernel<8>, gb, b, lds_blk, s, a, q, nblk); break;
-                }
-            } else switch (epl) {
-                case 1: hipLaunchKernelGGL(jac_persist_kernel<1>, g, b, 0, s, a, q); break;
-                case 2: hipLaunchKernelGGL(jac_persist_kernel<2>, g, b, 0, s, a, q); break;
-                case 4: hipLaunchKernelGGL(jac_persist_kernel<4>, g, b, 0, s, a, q); break;
-                case 8: hipLaunchKernelGGL(jac_persist_kernel<8>, g, b, 0, s, a, q); break;
-                default: hipLaunchKernelGGL(jac_persist_kernel<16>, g, b, 0, s, a, q); break;
-            }
-            PCHK(hipGetLastError());
-            int h[2] = {0, 0};
-            PCHK(hipMemcpyAsync(&h[0], q.sweeps, sizeof(int), hipMemcpyDeviceToHost, s));
-            PCHK(hipMemcpyAsync(&h[1], q.err, sizeof(int), hipMemcpyDeviceToHost, s));
-            PCHK(hipStreamSynchronize(s));
-            if (h[1]) {  // a barrier wait timed out: every workgroup has left; start over from X, one launch per round
-                PCHK(hipMemcpyAsync(X, Xbak, nv * sizeof(double2), hipMemcpyDeviceToDevice, s));
-                hipLaunchKernelGGL(jac_init_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, V, n);
-                persist = false;
-                g_jac_fallbacks.fetch_add(1);
-            } else {
-                sweeps = h[0];
-            }
+        bool done = false;
+        if (epl && env.jpersist != 0 && max_sweeps <= JC_MAX_SWEEPS) {
+            const int rc = jac_run_persistent(a, epl, env, cnt, Xbak, max_sweeps, done, sweeps, s);
+            if (rc) return rc;
         }
-        if (!persist) {
-            bool conv = false;
-            for (; sweeps < max_sweeps;) {
-                PCHK(hipMemsetAsync(cnt, 0, sizeof(int), s));
-                for (int t = 0; t < a.nn - 1; ++t)
-                    hipLaunchKernelGGL(jac_round_kernel, dim3((npair + wpb - 1) / wpb), dim3(64 * wpb), 0, s, a, t);
-                PCHK(hipGetLastError());
-                int h = 0;
-                PCHK(hipMemcpyAsync(&h, cnt, sizeof(int), hipMemcpyDeviceToHost, s));
-                PCHK(hipStreamSynchronize(s));
-                ++sweeps;
-                if (h == 0) { conv = true; break; }
-            }
-            if (!conv) sweeps = max_sweeps + 1;
+        if (!done) {
+            const int rc = jac_run_rounds(a, cnt, max_sweeps, sweeps, s);
+            if (rc) return rc;
         }
     }
     hipLaunchKernelGGL(jac_finish_kernel, dim3((n + 3) / 4), dim3(256), 0, s, X, n, sigma);
