@@ -250,12 +250,5 @@ hipError_t launch_dressed_n(const DressedParams& p, hipStream_t s) {
 }  // namespace
 
 hipError_t launch_dressed(int N, const DressedParams& p, hipStream_t s) {
-    switch (N) {
-        case 2: return launch_dressed_n<2>(p, s);
-        case 3: return launch_dressed_n<3>(p, s);
-        case 4: return launch_dressed_n<4>(p, s);
-        case 5: return launch_dressed_n<5>(p, s);
-        case 6: return launch_dressed_n<6>(p, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_list<2, 3, 4, 5, 6>(N, [&](auto NN) { return launch_dressed_n<KV(NN)>(p, s); });
 }

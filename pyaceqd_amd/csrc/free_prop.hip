@@ -412,13 +412,8 @@ template <int N2>
 hipError_t launch_fpm(const FreePropParams& p, hipStream_t s) {
     using F = FPM<N2>;
     const size_t lds = (p.n_sub > 1 ? 3 : 2) * F::MAT * sizeof(double2);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)free_prop_mfma_kernel<N2>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(3 * F::MAT * sizeof(double2)));
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    // the attribute at 3 matrices whatever n_sub is (lds is 2 or 3)
+    if (hipError_t e = allow_dyn_lds<&free_prop_mfma_kernel<N2>>(3 * F::MAT * sizeof(double2)); e != hipSuccess) return e;
     const long long nblk = p.idle_pass ? (long long)p.n_sys : 2LL * p.n_steps * p.n_sys;
     if (nblk <= 0) return hipSuccess;
     hipLaunchKernelGGL(free_prop_mfma_kernel<N2>, dim3((unsigned)std::min<long long>(nblk, FP_MAX_BLOCKS)), dim3(256),
@@ -674,13 +669,7 @@ __global__ __launch_bounds__(256) void free_win_kernel(FreePropParams p) {
 template <int N2>
 hipError_t launch_fp(const FreePropParams& p, hipStream_t s) {
     const size_t lds = 4ull * N2 * N2 * sizeof(double2);
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)free_prop_kernel<N2>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    if (hipError_t e = allow_dyn_lds<&free_prop_kernel<N2>>(lds); e != hipSuccess) return e;
     const long long nblk = p.idle_pass ? (long long)p.n_sys : 2LL * p.n_steps * p.n_sys;
     if (nblk <= 0) return hipSuccess;
     // A, P, T (+ Acc only for n_sub > 1): at N2 = 36, 62 KiB instead of 83 KiB lets two workgroups share a CU
@@ -890,14 +879,7 @@ hipError_t launch_fs(const FuseParams& p, hipStream_t s) {
 }  // namespace
 
 hipError_t launch_fuse_steps(int N2, const FuseParams& p, hipStream_t s) {
-    switch (N2) {
-        case 4: return launch_fs<4>(p, s);
-        case 9: return launch_fs<9>(p, s);
-        case 16: return launch_fs<16>(p, s);
-        case 25: return launch_fs<25>(p, s);
-        case 36: return launch_fs<36>(p, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_n2(N2, [&](auto NN) { return launch_fs<KV(NN)>(p, s); });
 }
 
 static hipError_t launch_free_prop_pass(int N2, const FreePropParams& p, hipStream_t s) {
@@ -916,14 +898,12 @@ static hipError_t launch_free_prop_pass(int N2, const FreePropParams& p, hipStre
                                dim3(256), 0, s, q);
         return hipGetLastError();
     }
-    switch (N2) {
-        case 4: return launch_fp<4>(p, s);
-        case 9: return launch_fp<9>(p, s);
-        case 16: return p.mfma ? launch_fpm<16>(p, s) : launch_fp<16>(p, s);
-        case 25: return p.mfma ? launch_fpm<25>(p, s) : launch_fp<25>(p, s);
-        case 36: return p.mfma ? launch_fpm<36>(p, s) : launch_fp<36>(p, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_n2(N2, [&](auto NN) {
+        if constexpr (KV(NN) >= 16) {  // the matrix-core kernel exists from N2 = 16 up
+            if (p.mfma) return launch_fpm<KV(NN)>(p, s);
+        }
+        return launch_fp<KV(NN)>(p, s);
+    });
 }
 
 // the pulse windows alone (plan creation decides from them whether windows pay, pqd_host.cpp)
@@ -946,12 +926,6 @@ hipError_t launch_free_prop(int N2, const FreePropParams& p, hipStream_t s) {
     }
     q.idle_pass = 0;
     if (!p.Midle) q.win = nullptr;  // windows need the idle propagator
-    if (q.win && p.n_steps > 0) {
-        hipLaunchKernelGGL(free_win_init_kernel, dim3((p.n_sys + 255) / 256), dim3(256), 0, s, q.win, p.n_sys);
-        const long long nblk = (long long)p.n_sys * ((2LL * p.n_steps + 255) / 256);
-        hipLaunchKernelGGL(free_win_kernel, dim3((unsigned)std::min<long long>(nblk, FP_MAX_BLOCKS)), dim3(256), 0, s,
-                           q);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
+    if (hipError_t e = launch_free_win(q, s); e != hipSuccess) return e;  // nothing without q.win or steps
     return launch_free_prop_pass(N2, q, s);
 }

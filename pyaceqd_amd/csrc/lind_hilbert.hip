@@ -126,8 +126,7 @@ __global__ __launch_bounds__(HB_NT_MAX) void lind_hilbert_kernel(HilbertParams p
 
 template <bool CSR_LDS, bool MAP>
 hipError_t hb_launch(int n_traj, const HilbertParams& p, hipStream_t s) {
-    static size_t allowed[32] = {};
-    hipError_t e = hb_allow_lds((const void*)lind_hilbert_kernel<CSR_LDS, MAP>, allowed, HB_LDS_MAX);
+    hipError_t e = allow_dyn_lds<&lind_hilbert_kernel<CSR_LDS, MAP>>(HB_LDS_MAX);
     if (e != hipSuccess) return e;
     const size_t lds = hb_mat_elems(p.N, p.nl_max) * sizeof(double2) + p.csr_lds;
     hipLaunchKernelGGL((lind_hilbert_kernel<CSR_LDS, MAP>), dim3(n_traj), dim3(hb_threads(p.N)), lds, s, p);

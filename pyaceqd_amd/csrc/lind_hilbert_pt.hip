@@ -207,8 +207,7 @@ __global__ __launch_bounds__(HBPT_NT_MAX) void lind_hilbert_pt_kernel(HilbertPtP
 
 template <bool CSR_LDS, bool MAP>
 hipError_t hp_launch(int n_traj, const HilbertPtParams& q, size_t lds, hipStream_t s) {
-    static size_t allowed[32] = {};
-    hipError_t e = hb_allow_lds((const void*)lind_hilbert_pt_kernel<CSR_LDS, MAP>, allowed, lds);
+    hipError_t e = allow_dyn_lds<&lind_hilbert_pt_kernel<CSR_LDS, MAP>>(lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((lind_hilbert_pt_kernel<CSR_LDS, MAP>), dim3(n_traj), dim3(q.G * hb_threads(q.h.N)), lds, s, q);
     return hipGetLastError();

@@ -719,6 +719,9 @@ __global__ __launch_bounds__(64) void dyn_t1_kernel(FourTimeParams p, double2* o
 
 }  // namespace
 
+// map rows prefetched ahead by the pipelined tau kernels (mc_tau_pipe_kernel, mcb_tau_kernel)
+constexpr int mc_pfd(int N2) { return N2 == 4 ? 4 : (N2 <= 16 ? 2 : 1); }
+
 hipError_t launch_mapchain(const MapChainParams& p, hipStream_t s) {
     hipLaunchKernelGGL(mc_trunk_kernel, dim3(1), dim3(64), 0, s, p);
     hipError_t e = hipGetLastError();
@@ -728,20 +731,17 @@ hipError_t launch_mapchain(const MapChainParams& p, hipStream_t s) {
     if (nblk <= 0 || p.n_tau <= 0) return hipGetLastError();
     const char* pe = getenv("PQD_MC_PIPE");
     if (!(pe && atoi(pe) == 0)) {
-        switch (p.N2) {
-            case 4: hipLaunchKernelGGL((mc_tau_pipe_kernel<4, 4>), dim3(nblk), dim3(64), 0, s, p); return hipGetLastError();
-            case 9: hipLaunchKernelGGL((mc_tau_pipe_kernel<9, 2>), dim3(nblk), dim3(64), 0, s, p); return hipGetLastError();
-            case 16: hipLaunchKernelGGL((mc_tau_pipe_kernel<16, 2>), dim3(nblk), dim3(64), 0, s, p); return hipGetLastError();
-            case 25: hipLaunchKernelGGL((mc_tau_pipe_kernel<25, 1>), dim3(nblk), dim3(64), 0, s, p); return hipGetLastError();
-            case 36: hipLaunchKernelGGL((mc_tau_pipe_kernel<36, 1>), dim3(nblk), dim3(64), 0, s, p); return hipGetLastError();
-            default: break;
-        }
+        const bool piped = dispatch_n2(p.N2, [&](auto NN) {
+            hipLaunchKernelGGL((mc_tau_pipe_kernel<KV(NN), mc_pfd(KV(NN))>), dim3(nblk), dim3(64), 0, s, p);
+            return true;
+        });
+        if (piped) return hipGetLastError();
     }
     hipLaunchKernelGGL(mc_tau_kernel, dim3(nblk), dim3(64), 0, s, p);
     return hipGetLastError();
 }
 
-template <int N2, int PFD>
+template <int N2, int PFD = mc_pfd(N2)>
 static hipError_t launch_blocked_n(const MapChainParams& p, int n_chain, hipStream_t s) {
     if (p.n_blk > 0) hipLaunchKernelGGL((mcb_prefix_kernel<N2>), dim3(p.n_blk), dim3(256), 0, s, p);
     constexpr int TPW = 64 / N2;
@@ -765,29 +765,17 @@ static hipError_t launch_blocked_n(const MapChainParams& p, int n_chain, hipStre
 // modes 0 and 1 on the blocked sweep; p.pos, p.L, p.n_blk, p.Q and the U / Rend / P / X buffers set by the host;
 // n_chain = max_i p_i / L block starts of the trunk (mode 0)
 hipError_t launch_mapchain_blocked(const MapChainParams& p, int n_chain, hipStream_t s) {
-    switch (p.N2) {
-        case 4: return launch_blocked_n<4, 4>(p, n_chain, s);
-        case 9: return launch_blocked_n<9, 2>(p, n_chain, s);
-        case 16: return launch_blocked_n<16, 2>(p, n_chain, s);
-        case 25: return launch_blocked_n<25, 1>(p, n_chain, s);
-        case 36: return launch_blocked_n<36, 1>(p, n_chain, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_n2(p.N2, [&](auto NN) { return launch_blocked_n<KV(NN)>(p, n_chain, s); });
 }
 
 hipError_t launch_map_tail(int N2, const double2* M, const double2* X, int n_x, const double2* w, int n_steps,
                            double2* out, hipStream_t s) {
     const int TPW = 64 / N2;
     const dim3 grid((n_x + TPW - 1) / TPW);
-    switch (N2) {
-        case 4: hipLaunchKernelGGL(map_tail_kernel<4>, grid, dim3(64), 0, s, M, X, n_x, w, n_steps, out); break;
-        case 9: hipLaunchKernelGGL(map_tail_kernel<9>, grid, dim3(64), 0, s, M, X, n_x, w, n_steps, out); break;
-        case 16: hipLaunchKernelGGL(map_tail_kernel<16>, grid, dim3(64), 0, s, M, X, n_x, w, n_steps, out); break;
-        case 25: hipLaunchKernelGGL(map_tail_kernel<25>, grid, dim3(64), 0, s, M, X, n_x, w, n_steps, out); break;
-        case 36: hipLaunchKernelGGL(map_tail_kernel<36>, grid, dim3(64), 0, s, M, X, n_x, w, n_steps, out); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_n2(N2, [&](auto NN) {
+        hipLaunchKernelGGL(map_tail_kernel<KV(NN)>, grid, dim3(64), 0, s, M, X, n_x, w, n_steps, out);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_propagate_tau(int N2, const double2* dm, const double2* rho0, int n_tau, int j_start,

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <climits>
+#include <type_traits>
+#include <utility>
 
 #define PQD_WAVE 64
 
@@ -376,16 +378,6 @@ inline bool hb_params_ok(const HilbertParams& p) {
 inline bool hb_map_params_ok(const HilbertParams& p, int n_traj) {
     return n_traj % (p.N * p.N) == 0 && p.map_ta && p.map_steps >= 1 && p.map_nev >= 0 && p.out;
 }
-// allows `kernel` lds bytes of dynamic LDS on the current device, unless `allowed` (the kernel's own record, one entry
-// per device: the attribute belongs to the device's copy of the kernel) shows it has that much already
-inline hipError_t hb_allow_lds(const void* kernel, size_t (&allowed)[32], size_t lds) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    if (dev < 32 && lds <= allowed[dev]) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess && dev < 32) allowed[dev] = lds;
-    return e;
-}
 hipError_t launch_hilbert(int n_traj, const HilbertParams& p, hipStream_t s);
 hipError_t launch_hilbert_map(int n_traj, const HilbertParams& p, hipStream_t s);  // n_traj = n_maps * N^2
 // dm[m][n][alpha][beta] = stage[((m N^2 + beta) n_steps + n) N^2 + alpha]: the states the map instances stored, as
@@ -498,6 +490,46 @@ bool quad_supported(int N2, int CHI);
 // ncg: 4-column groups per wave, 4 (strips of 16 columns, one wave per SIMD) or 2 (strips of 8, two waves per SIMD)
 int quad_qpw(int CHI, int qpw, int ncg);  // quads per workgroup launch_quad instantiates
 hipError_t launch_quad(int CHI, int n_quads, int qpw, int ncg, const SweepParams& p, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
+// launch layer shared by the .hip translation units: instance dispatch and the per-device dynamic-LDS attribute
+// ---------------------------------------------------------------------------------------------
+// what a dispatcher returns when no instance matches: hipErrorInvalidValue for a launcher, else 0 / false
+template <class R>
+constexpr R dispatch_miss() {
+    if constexpr (std::is_same_v<R, hipError_t>) return hipErrorInvalidValue;
+    else return R{};
+}
+// f(std::integral_constant<int, V>{}) for the listed V equal to v (f a generic lambda; KV(E) is its constant), or
+// dispatch_miss when v is not listed. (ptgen.hip's dispatch_pow2 differs on purpose: an unlisted value there runs the
+// last listed instance, each call site's fallback.)
+template <int V0, int... Vs, class F>
+auto dispatch_list(int v, F&& f) -> decltype(f(std::integral_constant<int, V0>{})) {
+    if (v == V0) return f(std::integral_constant<int, V0>{});
+    if constexpr (sizeof...(Vs) > 0) return dispatch_list<Vs...>(v, std::forward<F>(f));
+    else return dispatch_miss<decltype(f(std::integral_constant<int, V0>{}))>();
+}
+// the Liouville dimensions every N2-templated kernel is instantiated for (N = 2 .. 6)
+template <class F>
+auto dispatch_n2(int N2, F&& f) {
+    return dispatch_list<4, 9, 16, 25, 36>(N2, std::forward<F>(f));
+}
+constexpr bool n2_listed(int N2) { return N2 == 4 || N2 == 9 || N2 == 16 || N2 == 25 || N2 == 36; }
+#define KV(E) decltype(E)::value  // the constant a dispatch lambda was called with
+
+// allows the kernel K `lds` bytes of dynamic LDS on the current device, unless K's record (one entry per device: the
+// attribute belongs to the device's copy of the kernel) shows it has that much already. One record per kernel
+// instance, so a launch and an occupancy query of the same instance share it.
+template <auto K>
+hipError_t allow_dyn_lds(size_t lds) {
+    static size_t allowed[32] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
+    if (dev < 32 && lds <= allowed[dev]) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess && dev < 32) allowed[dev] = lds;
+    return e;
+}
 
 // consecutive 256-B aligned sub-buffers of one device allocation (size pass with base == nullptr)
 struct Carve {

@@ -11,13 +11,11 @@
 //   PT(n)     half h: y_b = r_b^h . S_alpha_h(n) for every active trajectory b, r_b^h = row alpha_h of F_b(n) Q_b
 //             (from the gather of step n - 1): thread (kq, d) holds S[kq KPER + j][d] (j < KPER) in registers; a
 //             wave's four 16-lane rows are the four k-groups of 16 columns, summed by permlane swaps
-//   publish   y_b -> exchange slot n & 1 of trajectory b (16-B stores that keep the line in the group's L2, or 8-B
-//             sc1 relaxed atomic stores: l2keep), every storing wave drains (s_waitcnt vmcnt(0)), a barrier, then ONE
-//             lane stores the workgroup's arrival word (= n + 1, with its XCD id)
+//   publish   y_b -> exchange slot n & 1 of trajectory b, then the workgroup arrives (split_handoff.h: publish, arrive)
 //   operands  F_b(n + 1) rows and the output rows W_b(n + 1) were loaded into registers during step n - 1: they go to
 //             LDS now and the loads of step n + 2's are issued (an operand load never sits between a publish and a
 //             poll); then the next slice rows when the schedule changes them
-//   poll      wave 0 reads the G arrival words of the group (one relaxed sc1 load per poll), the others wait at a barrier
+//   poll      wave 0 waits for the G arrival words of the group (split_handoff.h), the others wait at a barrier
 //   gather    half h takes the trajectories b = h, h + R, ...: every element of each state by 16-B sc1 buffer loads,
 //             up to 4 trajectories' loads in flight per thread; thread (kq, c, rg) takes column kq KPER + c of rows
 //             rg + 4 i (consecutive lanes consecutive columns) and contracts them with F_b(n + 1)[alpha][.] for all R
@@ -30,34 +28,18 @@
 // W'(n) = ovec S_before M_b(n - 1) (M_b(-1) = 1), built per event on the device after the free propagators
 // (evcomp_kernel), so each step of each trajectory is one row operator and one set of output rows (the batched
 // kernel's unfused sequence gives the same values to rounding).
-// Hand-off and residency as in pt_split.hip (MI355X_MICROARCH.md § visibility "Valid forms" row 1): payload stores
-// sc1, drain, barrier, arrival word; polls and payload loads sc1; one workgroup per CU by the LDS request and at most
-// n_cu workgroups (host check); every spin is bounded and a timeout ends the kernel with an error word, after which
-// the host re-runs the step range on the batched kernel.
-#include "pqd_common.h"
+// Hand-off and residency are pt_split.hip's, described once in split_handoff.h; after a timeout's error word the host
+// re-runs the step range on the batched kernel.
+#include "split_handoff.h"
 
 namespace {
 
-typedef unsigned long long __attribute__((address_space(1))) mu64;
-typedef unsigned int __attribute__((address_space(1))) mu32;
-typedef unsigned int v4u32m __attribute__((ext_vector_type(4)));
-
 constexpr int MS_LDS_FORCE = 96 * 1024;  // dynamic LDS request: one workgroup per CU
 constexpr int MS_CEV_MAX = 512;          // composite events per group held in LDS (msplit_cev_max)
-constexpr unsigned MS_STEP_MASK = 0x0FFFFFFFu;  // arrival word: step n + 1 in bits 0..27, the writer's XCD id above
-// s_getreg_b32 hwreg(HW_REG_XCC_ID, 0, 4): register id 20, offset 0, size 4 (simm16 = (size - 1) << 11 | offset << 6 | id)
-constexpr int MS_HWREG_XCC_ID = (3 << 11) | (0 << 6) | 20;
 template <int V>
 struct MsIC {  // compile-time int tag (the gather's chunk variants)
     static constexpr int value = V;
 };
-
-__device__ __forceinline__ void ms_st_sc1(double2* p, double2 v) {
-    __hip_atomic_store((mu64*)&p->x, (unsigned long long)__double_as_longlong(v.x), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store((mu64*)&p->y, (unsigned long long)__double_as_longlong(v.y), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // sum over the 4 row groups of a gather column (lanes 8 / 16 apart at KPER = 8, 16 / 32 apart otherwise), left in all
 // four lanes with the same bits (each step adds the same pair: row_ror:8 inside a 16-lane row, then permlane swaps)
@@ -89,26 +71,30 @@ __device__ __forceinline__ double2 ms_rg_sum2(double2 a, double2 b) {
     return make_double2(xor_add<32>(h.x), xor_add<32>(h.y));
 }
 
-// plain 16-B global store: the line stays in the XCD's L2 (an sc1 store drops it, and the same-XCD readers then fetch
-// it at the cross-XCD rate, MI355X_MICROARCH.md § visibility, store flavours). Used only where every workgroup of the
-// group runs on one XCD (checked at the first poll: see l2keep)
-__device__ __forceinline__ void ms_st_keep(double2* p, double2 v) {
-    typedef double v2f64 __attribute__((ext_vector_type(2)));
-    v2f64 w = {v.x, v.y};
-    *(__attribute__((address_space(1))) v2f64*)p = w;
-}
-
-// plain global load (global_load, not flat_load: a flat load also counts in lgkmcnt)
-__device__ __forceinline__ double2 ms_gld(const double2* p) {
-    const __attribute__((address_space(1))) double* q = (const __attribute__((address_space(1))) double*)p;
-    return make_double2(q[0], q[1]);
-}
-
 __device__ __forceinline__ double2 ms_wave_sum(double2 v) {
     v = c_group_sum<16>(v);
     v = make_double2(xor_add<16>(v.x), xor_add<16>(v.y));
     return make_double2(xor_add<32>(v.x), xor_add<32>(v.y));
 }
+
+// the instance set: rows per workgroup R of the instance (N2, CHI), 0 where there is none.
+// R = 2 (each trajectory's state gathered by half as many workgroups, the slice rows 128 KiB per CU at chi = 64 in the
+// registers of 512 threads), 1 at N2 = 9 (G = 9 keeps three groups per XCD). N2 = 25 at chi = 64 spills (7 gathered
+// rows per thread for two PT rows): the single split or batched kernels.
+// chi = 128 (the bond cap of generated N <= 4 PTs, which the single-trajectory split kernel does not take): one PT
+// row per workgroup of 512 threads, the 256 KiB slice row in their registers.
+// chi = 256 (a bond past the batched kernel's LDS: generated PTs whose threshold asks for more than 128, VERDICT r5
+// item 2b): one PT row per workgroup of 1,024 threads, the slice row streamed from L2 each step. N2 = 4 only there:
+// the two-level system's other bonds run on the quad and batched kernels.
+constexpr int ms_rows_of(int N2, int CHI) {
+    if (CHI == 256) return (N2 == 4 || N2 == 9 || N2 == 16) ? 1 : 0;
+    if (CHI == 128) return (N2 == 9 || N2 == 16) ? 1 : 0;
+    if (CHI != 32 && CHI != 64) return 0;
+    if (N2 == 9) return 1;
+    return (N2 == 16 || N2 == 36 || (N2 == 25 && CHI == 32)) ? 2 : 0;
+}
+// most trajectories per group
+constexpr int ms_tbmax_of(int CHI, int R) { return CHI > 64 ? 8 : (R == 1 ? 32 : (R == 2 ? 16 : 8)); }
 
 template <int N2, int CHI, int R>
 struct MsLayout {
@@ -122,7 +108,7 @@ struct MsLayout {
     static constexpr int EPT = (N2 + RG - 1) / RG;  // state rows per thread and trajectory in the gather
     static constexpr int GCH = CHI > 64 ? 1 : (R >= 4 ? 2 : (EPT <= 4 ? 4 : 1));  // trajectories per half with gather loads in flight
     static constexpr int PVR = (KPER + 15) / 16;   // registers of 16 row values (DPP row broadcast in the PT)
-    static constexpr int TBMAX = CHI > 64 ? 8 : (R == 1 ? 32 : (R == 2 ? 16 : 8));
+    static constexpr int TBMAX = ms_tbmax_of(CHI, R);
     static constexpr int OMAX = 8;                  // outputs per trajectory
     static constexpr int TMINE = (TBMAX + G - 1) / G;  // trajectories whose outputs one workgroup writes
     static constexpr int FPT = (R * TBMAX * N2 + NT - 1) / NT;      // F-row entries per thread
@@ -164,8 +150,7 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
     const int h = R == 1 ? 0 : __builtin_amdgcn_readfirstlane(tid / HT), ht = tid - h * HT;  // half (wave-uniform), thread in it
     int grp, g;
     if (q.xcd > 0) {
-        // XCD-grouped grid: block b sits in XCD slot b % 8 under the observed round-robin dealing; slot xs holds the
-        // groups xs, xs + 8, ... so each group's hand-offs stay in one L2 (speed only, as in pt_split.hip)
+        // XCD-grouped grid: split_handoff.h's xcd_slot, written out (the call moved SGPR spills here)
         const int xs = blockIdx.x & 7, loc = blockIdx.x >> 3;
         grp = xs + 8 * (loc / G);
         g = loc - (loc / G) * G;
@@ -210,17 +195,9 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
     double2* __restrict__ Xg = X + (size_t)grp * TB * 2 * E;
     const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(Xg, 0, TB * 2 * E * 16, 0x00020000);
     unsigned* ct = cnt + (size_t)grp * 64;
-    // l2keep (XCD-grouped grid): payload stores keep their lines in the XCD's L2, which is coherent for the readers'
-    // sc1 loads only if every workgroup of the group runs on that XCD. Each arrival word carries its writer's XCD id
-    // (bits 28..30, HW_REG_XCC_ID) and the first poll checks them; a group spread over XCDs ends the launch before its
-    // first gather (error words 0 and 1) and the host re-runs it with sc1 stores. PQD_ABLATE bit 512 fakes a spread
-    // group (workgroup 0 reports the next XCD) for the test of that path.
-    unsigned xtag = 0;
-    if (q.l2keep) {
-        unsigned xid = (unsigned)__builtin_amdgcn_s_getreg(MS_HWREG_XCC_ID) & 7u;
-        if ((p.ablate & 512) && g == 0) xid = (xid + 1u) & 7u;
-        xtag = xid << 28;
-    }
+    // l2keep (split_handoff.h): a group spread over XCDs ends the launch before its first gather (error words 0 and
+    // 1) and the host re-runs it with sc1 stores
+    const unsigned xtag = q.l2keep ? xcd_tag(g, p.ablate) : 0;
 
     // thread roles in its half: PT column j = 16 (wave in the half) + lane % 16 and the lane's 16-lane row kq. The
     // VALU PT (q.ptm = 0) holds slice rows kq KPER + jj of column j; the matrix-core PT (q.ptm = 1) holds rows
@@ -240,15 +217,12 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
         const double2* __restrict__ S = p.Q + ((size_t)si * p.D + grow) * CHI * CHI;
 #pragma unroll
         for (int jj = 0; jj < KPER; ++jj)
-            sreg[jj] = ms_gld(S + (size_t)(ptm ? 4 * jj + kq : kq * KPER + jj) * CHI + j);
+            sreg[jj] = gld(S + (size_t)(ptm ? 4 * jj + kq : kq * KPER + jj) * CHI + j);
     };
-    // the schedule, 64 entries per VGPR (lane i holds sched[64 c + i]) one chunk ahead, picked with v_readlane
-    auto sched_chunk = [&](int ch) {
-        const int i = 64 * ch + lane;
-        return i < n_end ? *(const __attribute__((address_space(1))) int*)(p.sched + i) : -1;
-    };
-    int sch_reg = sched_chunk(0);  // the chunk of sched[m] for the coming step's m = n + 1, loaded a step ahead
-    int cur_slice = n_end > 0 ? __builtin_amdgcn_readlane(sch_reg, 0) : -1;
+    // the schedule in 64-entry chunks (split_handoff.h): the chunk of sched[m] for the coming step's m = n + 1, loaded
+    // a step ahead
+    int sch_reg = sched_chunk(p.sched, 0, lane, n_end);
+    int cur_slice = n_end > 0 ? sched_pick(sch_reg, 0) : -1;
     if (n_end > 0) fetch_slice(cur_slice);
     __syncthreads();
 
@@ -264,8 +238,8 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
         const double2* __restrict__ Fr =
             (ci >= 0 ? q.Fev + (size_t)ci * m2 : fw_M(p, sy, fw_win(p, sy), 0, m2)) + (size_t)a * N2;
         double2 acc = c_zero();
-        for (int be = 0; be < N2; ++be) c_fma(acc, ms_gld(Fr + be), ms_gld(p.rho0 + be));
-        smem[L::PRO + (r * TBM + b) * L::PRS + k] = c_mul(acc, ms_gld(p.bond0 + k));
+        for (int be = 0; be < N2; ++be) c_fma(acc, gld(Fr + be), gld(p.rho0 + be));
+        smem[L::PRO + (r * TBM + b) * L::PRS + k] = c_mul(acc, gld(p.bond0 + k));
     }
     for (int e = tid; e < TB * n_out; e += NT) {
         const int b = e / n_out, k = e - b * n_out;
@@ -273,8 +247,8 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
         const int ci = comp0(b);
         const double2* __restrict__ W0 = ci >= 0 ? q.Wev + (size_t)ci * n_out * N2 : p.ovec;
         double2 r = c_zero(), bc = c_zero();
-        for (int be = 0; be < N2; ++be) c_fma(r, ms_gld(W0 + (size_t)k * N2 + be), ms_gld(p.rho0 + be));
-        for (int d = 0; d < CHI; ++d) c_fma(bc, ms_gld(p.bond0 + d), ms_gld(p.closure0 + d));
+        for (int be = 0; be < N2; ++be) c_fma(r, gld(W0 + (size_t)k * N2 + be), gld(p.rho0 + be));
+        for (int d = 0; d < CHI; ++d) c_fma(bc, gld(p.bond0 + d), gld(p.closure0 + d));
         p.out[s_wo[b] + k] = c_mul(r, bc);
     }
 
@@ -285,7 +259,7 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
         int o = 0;
         for (int b = 0; b < TB; ++b) { s_cvo[b] = o; o += s_eve[b] - s_evi[b]; }
         s_abort = o > MS_CEV_MAX;  // the host never launches such a group (msplit_cev_max); refuse rather than overrun
-        if (s_abort) __hip_atomic_store((mu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (s_abort) __hip_atomic_store((gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
     if (s_abort) return;
@@ -374,7 +348,7 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
                     s_fcur[0][i * NT + tid] = (pk & ~1023) | ci;
                 }
             }
-            fpre[i] = ms_gld(src);
+            fpre[i] = gld(src);
         }
 #pragma unroll
         for (int i = 0; i < L::WPT; ++i) {
@@ -394,7 +368,7 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
                     s_wcur[0][i * NT + tid] = (pk & ~1023) | ci;
                 }
             }
-            wpre[i] = ms_gld(src);
+            wpre[i] = gld(src);
         }
     };
     // every entry is written (out-of-range ones to a dummy slot): a load consumed on some paths only stays pending in
@@ -429,7 +403,7 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
         }
     };
     load_ops(1);
-    clv = ms_gld(p.closure + (size_t)(n_end > 0 ? cur_slice : 0) * CHI + (tid & (CHI - 1)));
+    clv = gld(p.closure + (size_t)(n_end > 0 ? cur_slice : 0) * CHI + (tid & (CHI - 1)));
     __syncthreads();
 
     for (int n = 0;; ++n) {
@@ -481,7 +455,7 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
                     for (int j0 = 0; j0 < KPER; j0 += PFS) {
                         double2 bq[PFS];
 #pragma unroll
-                        for (int u = 0; u < PFS; ++u) bq[u] = ms_gld(Sg + (size_t)4 * (j0 + u) * CHI);
+                        for (int u = 0; u < PFS; ++u) bq[u] = gld(Sg + (size_t)4 * (j0 + u) * CHI);
 #pragma unroll
                         for (int u = 0; u < PFS; ++u) kstep(j0 + u, bq[u]);
                     }
@@ -495,7 +469,7 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
                     if (b < TB && ((act >> b) & 1)) {
                         double2* dst = Xg + ((size_t)b * 2 + (n & 1)) * E + (size_t)alpha * CHI + j;
                         const double2 y = make_double2(p1[u] - p2[u], p3[u] - p1[u] - p2[u]);
-                        if (q.l2keep) ms_st_keep(dst, y); else ms_st_sc1(dst, y);
+                        if (q.l2keep) st_keep(dst, y); else st_sc1(dst, y);
                     }
                 }
             }
@@ -523,7 +497,7 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
                         acc = make_double2(xor_add<32>(acc.x), xor_add<32>(acc.y));
                         if (lane < 16) {
                             double2* dst = Xg + ((size_t)b * 2 + (n & 1)) * E + (size_t)alpha * CHI + j;
-                            if (q.l2keep) ms_st_keep(dst, acc); else ms_st_sc1(dst, acc);
+                            if (q.l2keep) st_keep(dst, acc); else st_sc1(dst, acc);
                         }
                     }
                 }
@@ -535,13 +509,7 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (tid == 0) {
-            // with the group's placement on one XCD verified (first poll, l2keep) the arrival word is a plain store
-            // too: its line stays in the group's L2, where the peers' sc1 polls find it without a fabric round trip
-            const unsigned av = ((unsigned)n + 1u) | xtag;
-            if (q.l2keep && n >= 1) *(__attribute__((address_space(1))) unsigned*)(ct + g) = av;
-            else __hip_atomic_store((mu32*)(ct + g), av, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        if (tid == 0) arrive_word(ct, g, n, xtag, q.l2keep);
         stamp(n, 2);
         // ---- operands of step n + 1 (loaded during step n - 1's gather) to LDS
         stage_ops();
@@ -557,9 +525,9 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
             } else {
                 load_ops(m + 1);  // entries past their window read rho0[0]
             }
-            const int ns = m < n_end ? __builtin_amdgcn_readlane(sch_reg, m & 63) : cur_slice;
-            sch_reg = sched_chunk((m + 1) >> 6);
-            clv = ms_gld(p.closure + (size_t)ns * CHI + (tid & (CHI - 1)));
+            const int ns = m < n_end ? sched_pick(sch_reg, m) : cur_slice;
+            sch_reg = sched_chunk(p.sched, (m + 1) >> 6, lane, n_end);
+            clv = gld(p.closure + (size_t)ns * CHI + (tid & (CHI - 1)));
             if (ns != cur_slice) {
                 fetch_slice(ns);
                 cur_slice = ns;
@@ -568,29 +536,15 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
         // ---- wait for the group (wave 0); the other waves store the outputs of step n meanwhile
         if (tid >= 64 && n >= 1) flush(n, 1);
         if (tid < 64) {
-            const unsigned want = (unsigned)n + 1u;
-            unsigned spins = 0;
-            bool ok = true;
             bool placed = true;
-            for (;;) {
-                const unsigned v =
-                    lane < G ? __hip_atomic_load((mu32*)(ct + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : want;
-                if (__all((v & MS_STEP_MASK) >= want)) {
-                    // first poll: every peer's XCD id is in its word; the same words reach every workgroup of the group,
-                    // so all of them take the same decision
-                    if (q.l2keep && n == 0) {
-                        const unsigned x0 = __builtin_amdgcn_readfirstlane(v) >> 28;
-                        placed = __all(lane >= G || (v >> 28) == x0);
-                    }
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > p.spin_limit) { ok = false; break; }
-            }
+            const bool ok = poll_group<G>(ct, lane, (unsigned)n + 1u, p.spin_limit, q.l2keep && n == 0, placed);
+            // (the pair goes through one struct: read as two plain locals it moved a VGPR and an SGPR spill at
+            // N2 = 9, chi = 128 and 256)
+            const struct { bool ok, placed; } r = {ok, placed};
             if (tid == 0) {
-                s_abort = ok && placed ? 0 : 1;
-                if (!placed) __hip_atomic_store((mu32*)(err + 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (s_abort) __hip_atomic_store((mu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                s_abort = r.ok && r.placed ? 0 : 1;
+                if (!r.placed) __hip_atomic_store((gu32*)(err + 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (s_abort) __hip_atomic_store((gu32*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
         __syncthreads();
@@ -628,7 +582,7 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
             // every slot's loads are issued and waited for on every path (an idle slot reads element 0, one line for the
             // whole wave): loads that are consumed on some paths only stay pending in the waitcnt pass across the loops,
             // and the waits it then puts in front of the next chunk's loads serialised the chunk's round trips
-            v4u32m xr[GC][EPT];
+            v4u32 xr[GC][EPT];
             // timing-only variants (STAMP builds): 2048 rotates the chunk's trajectory order by the workgroup index,
             // 1024 points every gather load at element 0, 8192 those of half 1 (results not used)
             int rot = 0;
@@ -667,8 +621,7 @@ __global__ __launch_bounds__(4 * CHI * R) void pt_msplit_kernel(SweepParams p, M
                 double2 xv[EPT];
 #pragma unroll
                 for (int i = 0; i < EPT; ++i)
-                    xv[i] = make_double2(__hiloint2double((int)xr[bb][i].y, (int)xr[bb][i].x),
-                                         __hiloint2double((int)xr[bb][i].w, (int)xr[bb][i].z));
+                    xv[i] = unpack_c128(xr[bb][i]);
                 // the operand entries of a row are read from LDS together and then used (read one by one next to
                 // their products, each read's latency was exposed: ≈9,300 cycles for 8 trajectories' rows)
                 if ((nxt >> b) & 1) {
@@ -790,8 +743,8 @@ __global__ __launch_bounds__(256) void evcomp_kernel(SweepParams p, MsplitParams
         __syncthreads();
         for (int i = tid; i < m2; i += 256) {
             const int r = i / N2, c = i - r * N2;
-            A[i] = s >= 1 ? ms_gld(fw_M(p, sy, wn, 2 * (s - 1) + 1, m2) + i) : make_double2(r == c ? 1.0 : 0.0, 0.0);
-            if (ce.y >= 0) B[i] = ms_gld(p.sop + (size_t)ce.y * m2 + i);
+            A[i] = s >= 1 ? gld(fw_M(p, sy, wn, 2 * (s - 1) + 1, m2) + i) : make_double2(r == c ? 1.0 : 0.0, 0.0);
+            if (ce.y >= 0) B[i] = gld(p.sop + (size_t)ce.y * m2 + i);
         }
         __syncthreads();
         auto mul = [&](const double2* Lm, const double2* Rm, double2* Out) {  // Out = Lm Rm (LDS, all threads)
@@ -808,19 +761,19 @@ __global__ __launch_bounds__(256) void evcomp_kernel(SweepParams p, MsplitParams
         for (int i = tid; i < p.n_out * N2; i += 256) {
             const int k = i / N2, c = i - k * N2;
             double2 acc = c_zero();
-            for (int b = 0; b < N2; ++b) c_fma(acc, ms_gld(p.ovec + (size_t)k * N2 + b), P[b * N2 + c]);
+            for (int b = 0; b < N2; ++b) c_fma(acc, gld(p.ovec + (size_t)k * N2 + b), P[b * N2 + c]);
             q.Wev[(size_t)e * p.n_out * N2 + i] = acc;
         }
         double2* Rb = P == A ? Cm : A;  // the free buffer
         if (ce.z >= 0) {
             __syncthreads();
-            for (int i = tid; i < m2; i += 256) B[i] = ms_gld(p.sop + (size_t)ce.z * m2 + i);
+            for (int i = tid; i < m2; i += 256) B[i] = gld(p.sop + (size_t)ce.z * m2 + i);
             __syncthreads();
             mul(B, P, Rb);
             double2* t = P; P = Rb; Rb = t;
         }
         __syncthreads();
-        for (int i = tid; i < m2; i += 256) B[i] = s < n_steps ? ms_gld(fw_M(p, sy, wn, 2 * s, m2) + i) : c_zero();
+        for (int i = tid; i < m2; i += 256) B[i] = s < n_steps ? gld(fw_M(p, sy, wn, 2 * s, m2) + i) : c_zero();
         __syncthreads();
         mul(B, P, Rb);
         for (int i = tid; i < m2; i += 256) q.Fev[(size_t)e * m2 + i] = Rb[i];
@@ -834,122 +787,55 @@ hipError_t launch_ms_t(const SweepParams& p, const MsplitParams& q, double2* X, 
     if constexpr (!STAMP && N2 == 16 && CHI == 64) {
         if (p.ablate & 64) return launch_ms_t<N2, CHI, R, true>(p, q, X, cnt, err, s);
     }
-    static unsigned attr = 0;  // per-device bitmask
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    if (dev >= 32 || !(attr & (1u << dev))) {
-        hipError_t e = hipFuncSetAttribute((const void*)pt_msplit_kernel<N2, CHI, R, STAMP>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::LDS);
-        if (e != hipSuccess) return e;
-        if (dev < 32) attr |= 1u << dev;
-    }
+    if (hipError_t e = allow_dyn_lds<&pt_msplit_kernel<N2, CHI, R, STAMP>>(L::LDS); e != hipSuccess) return e;
     const int n_blocks = q.xcd > 0 ? 8 * q.xcd * L::G : q.n_groups * L::G;
     hipLaunchKernelGGL((pt_msplit_kernel<N2, CHI, R, STAMP>), dim3(n_blocks), dim3(L::NT), L::LDS, s, p, q, X, cnt,
                        err);
     return hipGetLastError();
 }
 
-template <int N2, int CHI, int R>
-int ms_occ_t() {
-    using L = MsLayout<N2, CHI, R>;
-    if (hipFuncSetAttribute((const void*)pt_msplit_kernel<N2, CHI, R>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)L::LDS) != hipSuccess)
-        return 0;
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pt_msplit_kernel<N2, CHI, R>, L::NT, L::LDS) != hipSuccess)
-        return 0;
-    return nb;
-}
-
-// rows per workgroup: 2 (each trajectory's state gathered by half as many workgroups, the slice rows 128 KiB per CU
-// at chi = 64 in the registers of 512 threads), 1 at N2 = 9 (G = 9 keeps three groups per XCD)
-constexpr int ms_rows(int N2) { return N2 == 9 ? 1 : 2; }
-
-template <int N2>
-hipError_t launch_ms_n(int CHI, const SweepParams& p, const MsplitParams& q, double2* X, unsigned* cnt,
-                       unsigned* err, hipStream_t s) {
-    if constexpr (N2 == 4) {  // chi = 256 only
-        return CHI == 256 ? launch_ms_t<4, 256, 1>(p, q, X, cnt, err, s) : hipErrorInvalidValue;
-    } else {
-    switch (CHI) {
-        case 32: return launch_ms_t<N2, 32, ms_rows(N2)>(p, q, X, cnt, err, s);
-        case 64:
-            if constexpr (N2 != 25) return launch_ms_t<N2, 64, ms_rows(N2)>(p, q, X, cnt, err, s);
-            return hipErrorInvalidValue;
-        case 128:
-            if constexpr (N2 <= 16) return launch_ms_t<N2, 128, 1>(p, q, X, cnt, err, s);
-            return hipErrorInvalidValue;
-        case 256:
-            if constexpr (N2 <= 16) return launch_ms_t<N2, 256, 1>(p, q, X, cnt, err, s);
-            return hipErrorInvalidValue;
-        default: return hipErrorInvalidValue;
-    }
-    }
-}
-
-template <int N2>
-int ms_occ_n(int CHI) {
-    if constexpr (N2 == 4) {
-        return CHI == 256 ? ms_occ_t<4, 256, 1>() : 0;
-    } else {
-    switch (CHI) {
-        case 32: return ms_occ_t<N2, 32, ms_rows(N2)>();
-        case 64:
-            if constexpr (N2 != 25) return ms_occ_t<N2, 64, ms_rows(N2)>();
-            return 0;
-        case 128:
-            if constexpr (N2 <= 16) return ms_occ_t<N2, 128, 1>();
-            return 0;
-        case 256:
-            if constexpr (N2 <= 16) return ms_occ_t<N2, 256, 1>();
-            return 0;
-        default: return 0;
-    }
-    }
+// f(N2 constant, CHI constant, R constant) for the instance of (N2, CHI), a miss (of type Ret) where none exists
+template <class Ret, class F>
+Ret ms_dispatch(int N2, int CHI, F&& f) {
+    return dispatch_n2(N2, [&](auto NN) {
+        return dispatch_list<32, 64, 128, 256>(CHI, [&](auto C) -> Ret {
+            constexpr int R = ms_rows_of(KV(NN), KV(C));
+            if constexpr (R > 0) return f(NN, C, std::integral_constant<int, R>{});
+            else return dispatch_miss<Ret>();
+        });
+    });
 }
 
 }  // namespace
 
-int msplit_rows(int N2, int CHI) { return CHI > 64 ? 1 : ms_rows(N2); }
-// (N2 = 4 only at chi = 256: the two-level system's other bonds run on the quad and batched kernels)
-int msplit_tbmax(int N2, int CHI) { return CHI > 64 ? 8 : (ms_rows(N2) == 1 ? 32 : 16); }
+int msplit_rows(int N2, int CHI) { return ms_rows_of(N2, CHI); }
+int msplit_tbmax(int N2, int CHI) { return ms_rows_of(N2, CHI) ? ms_tbmax_of(CHI, ms_rows_of(N2, CHI)) : 0; }
 int msplit_cev_max() { return MS_CEV_MAX; }
-int msplit_group_size(int N2, int CHI) { return (N2 + msplit_rows(N2, CHI) - 1) / msplit_rows(N2, CHI); }
-
-bool msplit_supported(int N2, int CHI, int n_out) {
-    // N2 = 25 at chi = 64 spills (7 gathered rows per thread for two PT rows): the single split or batched kernels
-    // chi = 128 (the bond cap of generated N <= 4 PTs, which the single-trajectory split kernel does not take): one PT
-    // row per workgroup of 512 threads, the 256 KiB slice row in their registers
-    // chi = 256 (a bond past the batched kernel's LDS: generated PTs whose threshold asks for more than 128, VERDICT r5
-    // item 2b): one PT row per workgroup of 1,024 threads, the slice row streamed from L2 each step
-    if (CHI == 256) return (N2 == 4 || N2 == 9 || N2 == 16) && n_out >= 1 && n_out <= 8;
-    return (N2 == 9 || N2 == 16 || N2 == 25 || N2 == 36) &&
-           (CHI == 32 || (CHI == 64 && N2 != 25) || (CHI == 128 && N2 <= 16)) && n_out >= 1 && n_out <= 8;
+int msplit_group_size(int N2, int CHI) {
+    const int R = ms_rows_of(N2, CHI);
+    return R ? (N2 + R - 1) / R : 0;
 }
+bool msplit_supported(int N2, int CHI, int n_out) { return ms_rows_of(N2, CHI) > 0 && n_out >= 1 && n_out <= 8; }
 
 int msplit_blocks_per_cu(int N2, int CHI) {
-    switch (N2) {
-        case 4: return ms_occ_n<4>(CHI);
-        case 9: return ms_occ_n<9>(CHI);
-        case 16: return ms_occ_n<16>(CHI);
-        case 25: return ms_occ_n<25>(CHI);
-        case 36: return ms_occ_n<36>(CHI);
-        default: return 0;
-    }
+    return ms_dispatch<int>(N2, CHI, [](auto NN, auto C, auto RR) {
+        using L = MsLayout<KV(NN), KV(C), KV(RR)>;
+        constexpr auto K = &pt_msplit_kernel<KV(NN), KV(C), KV(RR)>;
+        int nb = 0;
+        if (allow_dyn_lds<K>(L::LDS) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K, L::NT, L::LDS) != hipSuccess)
+            return 0;
+        return nb;
+    });
 }
 
 hipError_t launch_evcomp(int N2, const SweepParams& p, const MsplitParams& q, int n_cev, int n_steps, hipStream_t s) {
     if (n_cev <= 0) return hipSuccess;
     const dim3 grid((unsigned)(n_cev < 4096 ? n_cev : 4096));
-    switch (N2) {
-        case 4: hipLaunchKernelGGL((evcomp_kernel<4>), grid, dim3(256), 0, s, p, q, n_cev, n_steps); break;
-        case 9: hipLaunchKernelGGL((evcomp_kernel<9>), grid, dim3(256), 0, s, p, q, n_cev, n_steps); break;
-        case 16: hipLaunchKernelGGL((evcomp_kernel<16>), grid, dim3(256), 0, s, p, q, n_cev, n_steps); break;
-        case 25: hipLaunchKernelGGL((evcomp_kernel<25>), grid, dim3(256), 0, s, p, q, n_cev, n_steps); break;
-        case 36: hipLaunchKernelGGL((evcomp_kernel<36>), grid, dim3(256), 0, s, p, q, n_cev, n_steps); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_n2(N2, [&](auto NN) {
+        hipLaunchKernelGGL((evcomp_kernel<KV(NN)>), grid, dim3(256), 0, s, p, q, n_cev, n_steps);
+        return hipGetLastError();
+    });
 }
 
 // X: n_groups * TB * 2 * N2 * CHI double2; cnt: n_groups * 64 arrival words; err: 4 words (all zeroed here)
@@ -959,14 +845,9 @@ hipError_t launch_msplit(int N2, int CHI, const SweepParams& p, const MsplitPara
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(err, 0, 4 * sizeof(unsigned), s);
     if (e != hipSuccess) return e;
-    switch (N2) {
-        case 4: return launch_ms_n<4>(CHI, p, q, X, cnt, err, s);
-        case 9: return launch_ms_n<9>(CHI, p, q, X, cnt, err, s);
-        case 16: return launch_ms_n<16>(CHI, p, q, X, cnt, err, s);
-        case 25: return launch_ms_n<25>(CHI, p, q, X, cnt, err, s);
-        case 36: return launch_ms_n<36>(CHI, p, q, X, cnt, err, s);
-        default: return hipErrorInvalidValue;
-    }
+    return ms_dispatch<hipError_t>(N2, CHI, [&](auto NN, auto C, auto RR) {
+        return launch_ms_t<KV(NN), KV(C), KV(RR)>(p, q, X, cnt, err, s);
+    });
 }
 
 // diagnostics: the stamps of the last PQD_ABLATE=64 multi-trajectory split launch (2 workgroups x 16 steps x 32 slots)

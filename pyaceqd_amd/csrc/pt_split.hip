@@ -8,12 +8,9 @@
 // column phases (M_b(n-1), MTOs, outputs, M_a(n), or the fused F(n) = M_a(n) M_b(n-1)) mix rows, so
 // every workgroup gathers the whole state (N2 x chi, 16 KiB at C3) once per step and runs them
 // redundantly — ONE exchange per step instead of a row/column transpose pair.
-// Hand-off (default): arrival words. Payload stores are 8-B sc1 atomics, the storing wave drains with
-// s_waitcnt vmcnt(0), a workgroup barrier, then ONE lane stores the workgroup's arrival word (steps published; groups
-// of more than 32 workgroups add to one shared counter instead); wave 0 polls every word of the group with one relaxed
-// sc1 load per poll, the other waves wait at a barrier, and every payload load is an sc1 load — so no fences
-// (MI355X_MICROARCH.md § visibility "Valid forms" table row 1). With the XCD-grouped grid the counter form beat the
-// granule form below (C3 5.02 vs 5.33 us per step, profiles/r04/split/xcd/).
+// Hand-off (default): arrival words, the protocol of split_handoff.h (groups of more than 32 workgroups add to one
+// shared counter instead). With the XCD-grouped grid the counter form beat the granule form below (C3 5.02 vs 5.33 us
+// per step, profiles/r04/split/xcd/).
 // Output workgroup (default in the counter form, PQD_SPLIT_OW=0 off): the group gets one more workgroup, g = N2, that
 // owns no PT row. It gathers the state like its peers, writes the outputs and trunk checkpoints, and arrives at the
 // top of each step (it has read the previous slot); without it workgroup 0 ran the output pass between its publish
@@ -23,40 +20,19 @@
 // {tag = step + 1, word} granule written by ONE relaxed agent-scope atomic store (global_store_dwordx2 sc1); the
 // consumers sweep the whole state's granules with sc1 loads and re-read the ones whose tag is not yet the step's,
 // until every tag matches: no drain, no counter, no barrier between publishing and reading.
-// Either exchange buffer is double-buffered by step parity (a workgroup cannot publish step n+2 before every
-// peer has gathered step n: its step n+1 row depends on that gather; the output workgroup's arrival at step n+1
-// says it has gathered step n). One workgroup per CU (the LDS request
-// forces it) and at most n_cu workgroups (host check), so every workgroup is resident; every spin is bounded
-// and a timeout ends the kernel with an error word the host turns into PQD_ERR_HIP (then the batched kernel).
+// Either exchange buffer is double-buffered by step parity (split_handoff.h; the output workgroup's arrival at step
+// n + 1 says it has gathered step n). Residency and the bounded spins are the header's too: a timeout ends the kernel
+// with an error word the host turns into PQD_ERR_HIP (then the batched kernel).
 // Semantics are the sweep's: step n applies M_b(n-1), applyBefore MTOs at n,
 // output(n), applyAfter MTOs at n, M_a(n), PT(n); steps without MTOs use F(n) and read the outputs
 // through W(n) = ovec M_b(n-1), as the batched kernel does.
-#include "pqd_common.h"
+#include "split_handoff.h"
 #include <cstdlib>
 
 namespace {
 
-typedef unsigned long long __attribute__((address_space(1))) gu64;
-typedef unsigned int __attribute__((address_space(1))) gu32;
-
 constexpr int SP_NT = 256;
 constexpr int SP_LDS_FORCE = 96 * 1024;  // dynamic LDS request: one workgroup per CU
-
-__device__ __forceinline__ void st_sc1(double2* p, double2 v) {
-    __hip_atomic_store((gu64*)&p->x, (unsigned long long)__double_as_longlong(v.x), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store((gu64*)&p->y, (unsigned long long)__double_as_longlong(v.y), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// plain global load (a generic pointer would become flat_load, which also counts in lgkmcnt: every LDS wait
-// would then wait for the register prefetches too)
-__device__ __forceinline__ double2 gld(const double2* p) {
-    const __attribute__((address_space(1))) double* q = (const __attribute__((address_space(1))) double*)p;
-    return make_double2(q[0], q[1]);
-}
-
-typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
 
 // one granule: {tag, word} in ONE aligned 8-B sc1 store
 __device__ __forceinline__ void st_granule(unsigned long long* g, unsigned tag, unsigned word) {
@@ -105,12 +81,9 @@ __global__ __launch_bounds__(SP_NT) void pt_split_kernel(SweepParams p, double2*
     const int tid = threadIdx.x;
     int tl = blockIdx.x / G, g = blockIdx.x - tl * G;
     if (p.split_xcd > 0) {
-        // XCD-grouped grid (launch_split_tg): block b sits in XCD slot b % 8 under the observed round-robin dealing;
-        // group tl = slot + 8 (b / 8 / G) keeps all G workgroups of a group in one slot, so the group's hand-offs
-        // stay in one L2 when the dealing holds. Placement is speed only: the exchange is the same at any placement.
-        const int xs = blockIdx.x & 7, loc = blockIdx.x >> 3;
-        tl = xs + 8 * (loc / G);
-        g = loc - (loc / G) * G;
+        const XcdSlot xs = xcd_slot(blockIdx.x, G);  // XCD-grouped grid (launch_split_tg)
+        tl = xs.group;
+        g = xs.g;
         if (tl >= p.split_xcd) return;  // an unused block (before any shared state is touched)
     }
     const bool ow = OWG && g == N2;
@@ -129,30 +102,19 @@ __global__ __launch_bounds__(SP_NT) void pt_split_kernel(SweepParams p, double2*
     unsigned long long* __restrict__ Gt = reinterpret_cast<unsigned long long*>(Xt);
     // descriptor over this trajectory's granules, from workgroup-uniform values only (16-B sc1 loads of 2 granules)
     const __amdgpu_buffer_rsrc_t rG = __builtin_amdgcn_make_buffer_rsrc(Xt, 0, 4 * E * 16, 0x00020000);
-    // counter form: the group's arrival flags, one word per workgroup (flag g = steps workgroup g has published; the
-    // output workgroup's = steps it has gathered + 1), two 128-B lines per group. One word per producer instead of one
-    // shared counter: no serialised atomics at the L2, and wave 0 reads every flag with ONE load per poll. A group of
-    // more than 32 workgroups (N2 = 36: 37) spans two XCDs and two lines of flags; there one monotonic counter (one
-    // add per arrival, G per step) measured faster (C5 single run 43.1 -> 38.6-40.5 ms, profiles/r05/hyb/)
+    // counter form: the group's arrival words (word g = steps workgroup g has published; the output workgroup's = steps
+    // it has gathered + 1). A group of more than 32 workgroups (N2 = 36: 37) spans two XCDs and two lines of words;
+    // there one monotonic counter (one add per arrival, G per step) measured faster (C5 single run 43.1 -> 38.6-40.5
+    // ms, profiles/r05/hyb/)
     constexpr bool FLAGS = G <= 32;
     unsigned* ct = cnt + (size_t)t * 64;
-    // l2k (counter form with flags, XCD-grouped grid): the payload and, from the second step on, the arrival words are
-    // plain stores that keep their lines in the group's L2, where the peers' sc1 loads find them. That is coherent only
-    // if the whole group runs on one XCD: every flag carries its writer's XCD id (bits 28..30, HW_REG_XCC_ID) and the
-    // first poll checks them; a group spread over XCDs ends the launch before its first gather (error word), and the
-    // host re-runs it on the batched kernel. PQD_ABLATE bit 512 fakes a spread group (workgroup 0 reports the next XCD)
+    // l2k (counter form with words, XCD-grouped grid): split_handoff.h's l2keep. A group spread over XCDs ends the
+    // launch before its first gather (error word), and the host re-runs it on the batched kernel
     const bool l2k = FLAGS && !GRAN && p.split_xcd > 0 && p.split_l2 != 0;
-    unsigned xtag = 0;
-    if (l2k) {
-        unsigned xid = (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;  // hwreg(HW_REG_XCC_ID, 0, 4)
-        if ((p.ablate & 512) && g == 0) xid = (xid + 1u) & 7u;
-        xtag = xid << 28;
-    }
+    const unsigned xtag = l2k ? xcd_tag(g, p.ablate) : 0;
     auto arrive = [&](int n) {
         if constexpr (FLAGS) {
-            const unsigned av = ((unsigned)n + 1u) | xtag;
-            if (l2k && n >= 1) *(__attribute__((address_space(1))) unsigned*)(ct + g) = av;
-            else __hip_atomic_store((gu32*)(ct + g), av, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            arrive_word(ct, g, n, xtag, l2k);
         } else {
             __hip_atomic_fetch_add((gu32*)ct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -304,10 +266,8 @@ __global__ __launch_bounds__(SP_NT) void pt_split_kernel(SweepParams p, double2*
 #pragma unroll
         for (int j = 0; j < KPER; ++j) sreg[j] = gld(S + (size_t)(kq * KPER + j) * CHI + dcol);
     };
-    // the schedule, 64 entries at a time in a VGPR (lane i holds sched[64 c + i]) one chunk ahead, picked with
-    // v_readlane: a uniform p.sched[n] load in the loop compiles to a vector load + readfirstlane that waits
-    // (s_waitcnt vmcnt(0)) for every outstanding vector memory op where it is issued — on every workgroup's critical
-    // path each step
+    // the schedule in 64-entry chunks, the current one and the next: split_handoff.h's sched_chunk and sched_pick,
+    // written out (the calls moved SGPR spills here)
     auto sched_chunk = [&](int c) {
         const int i = 64 * c + lane;
         return i < n_end ? *(const __attribute__((address_space(1))) int*)(p.sched + i) : -1;
@@ -414,7 +374,7 @@ __global__ __launch_bounds__(SP_NT) void pt_split_kernel(SweepParams p, double2*
                     double2 y = smem[REDO + tid];
 #pragma unroll
                     for (int q = 1; q < KG; ++q) y = c_add(y, smem[REDO + q * CHI + tid]);
-                    if (l2k) {
+                    if (l2k) {  // st_keep, written out: the call moved VGPRs here
                         typedef double v2f64 __attribute__((ext_vector_type(2)));
                         *(__attribute__((address_space(1))) v2f64*)(Xn + (size_t)g * CHI + tid) = v2f64{y.x, y.y};
                     } else {
@@ -505,6 +465,8 @@ __global__ __launch_bounds__(SP_NT) void pt_split_kernel(SweepParams p, double2*
             ostage();  // visible to output(n + 1) after the column phase's barriers
         } else {
             if (tid < 64) {
+                // split_handoff.h's poll_group, written out (the call moved VGPRs and SGPR spills here), with the
+                // single counter of a group of more than 32 workgroups beside it; a placement miss is a failed wait
                 const unsigned want = (unsigned)n + 1u;
                 unsigned spins = 0;
                 bool ok = true;
@@ -513,8 +475,8 @@ __global__ __launch_bounds__(SP_NT) void pt_split_kernel(SweepParams p, double2*
                         const unsigned v =
                             lane < G ? __hip_atomic_load((gu32*)(ct + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                      : want;
-                        if (__all((v & 0x0FFFFFFFu) >= want)) {
-                            if (l2k && !placed_checked) {  // the same words reach every workgroup: one decision
+                        if (__all((v & HO_STEP_MASK) >= want)) {
+                            if (l2k && !placed_checked) {
                                 const unsigned x0 = __builtin_amdgcn_readfirstlane(v) >> 28;
                                 if (!__all(lane >= G || (v >> 28) == x0)) { ok = false; break; }
                             }
@@ -547,10 +509,7 @@ __global__ __launch_bounds__(SP_NT) void pt_split_kernel(SweepParams p, double2*
                 xr[i] = __builtin_amdgcn_raw_buffer_load_b128(rG, (int)(((size_t)(n & 1) * E + (e >= 0 ? e : 0)) * 16),
                                                               0, 16);
             }
-            auto xel = [&](int i) {
-                return make_double2(__hiloint2double((int)xr[i].y, (int)xr[i].x),
-                                    __hiloint2double((int)xr[i].w, (int)xr[i].z));
-            };
+            auto xel = [&](int i) { return unpack_c128(xr[i]); };
             if (pre && !ow && rowg) {
                 // a fused step next: only row g of F(n + 1) Q is needed, y[d] = sum_b F[g][b] Q[b][d]
                 double2 part = c_zero();
@@ -587,15 +546,7 @@ hipError_t launch_split_tg(int n_traj, const SweepParams& p, double2* X, unsigne
     if constexpr (!STAMP && !GRAN && N2 == 16 && CHI == 64) {
         if (p.ablate & 32) return launch_split_tg<N2, CHI, GRAN, OWG, true>(n_traj, p, X, cnt, err, s);
     }
-    static unsigned attr = 0;  // per-device bitmask (a second device needs the attribute set too)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    if (dev >= 32 || !(attr & (1u << dev))) {
-        hipError_t e = hipFuncSetAttribute((const void*)pt_split_kernel<N2, CHI, GRAN, OWG, STAMP>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::LDS);
-        if (e != hipSuccess) return e;
-        if (dev < 32) attr |= 1u << dev;
-    }
+    if (hipError_t e = allow_dyn_lds<&pt_split_kernel<N2, CHI, GRAN, OWG, STAMP>>(L::LDS); e != hipSuccess) return e;
     // XCD-grouped grid when every XCD slot can hold its groups at one workgroup per CU (32 CUs per XCD on MI355X):
     // 8 slots x ceil(n_traj / 8) groups x G blocks, the blocks of missing groups return at once
     const int per_slot = (n_traj + 7) / 8;
@@ -620,37 +571,17 @@ hipError_t launch_split_t(int n_traj, const SweepParams& p, double2* X, unsigned
                       : launch_split_tg<N2, CHI, false, false>(n_traj, p, X, cnt, err, s);
 }
 
-template <int N2>
-hipError_t launch_split_n(int CHI, int n_traj, const SweepParams& p, double2* X, unsigned* cnt, unsigned* err,
-                          hipStream_t s) {
-    switch (CHI) {
-        case 16: return launch_split_t<N2, 16>(n_traj, p, X, cnt, err, s);
-        case 32: return launch_split_t<N2, 32>(n_traj, p, X, cnt, err, s);
-        case 64: return launch_split_t<N2, 64>(n_traj, p, X, cnt, err, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-template <int N2, int CHI>
-int split_occ_t() {
-    using L = SplitLayout<N2, CHI>;
-    if (hipFuncSetAttribute((const void*)pt_split_kernel<N2, CHI, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)L::LDS) != hipSuccess)
-        return 0;
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pt_split_kernel<N2, CHI, false, true>, SP_NT, L::LDS) != hipSuccess)
-        return 0;
-    return nb;
-}
-
-template <int N2>
-int split_occ_n(int CHI) {
-    switch (CHI) {
-        case 16: return split_occ_t<N2, 16>();
-        case 32: return split_occ_t<N2, 32>();
-        case 64: return split_occ_t<N2, 64>();
-        default: return 0;
-    }
+// the instance set: every listed N2 at these bond dimensions
+constexpr bool split_instance(int N2, int CHI) { return n2_listed(N2) && (CHI == 16 || CHI == 32 || CHI == 64); }
+// f(N2 constant, CHI constant) for the instance of (N2, CHI), a miss where none exists
+template <class F>
+auto split_dispatch(int N2, int CHI, F&& f) {
+    return dispatch_n2(N2, [&](auto NN) {
+        return dispatch_list<16, 32, 64>(CHI, [&](auto C) {
+            static_assert(split_instance(KV(NN), KV(C)));
+            return f(NN, C);
+        });
+    });
 }
 
 }  // namespace
@@ -660,20 +591,19 @@ int split_group_size(int N2, bool ow) { return N2 + (ow ? 1 : 0); }
 
 // workgroups of the split kernel the runtime can keep resident per CU (0: the kernel cannot run)
 int split_blocks_per_cu(int N2, int CHI) {
-    switch (N2) {
-        case 4: return split_occ_n<4>(CHI);
-        case 9: return split_occ_n<9>(CHI);
-        case 16: return split_occ_n<16>(CHI);
-        case 25: return split_occ_n<25>(CHI);
-        case 36: return split_occ_n<36>(CHI);
-        default: return 0;
-    }
+    return split_dispatch(N2, CHI, [](auto NN, auto C) {
+        using L = SplitLayout<KV(NN), KV(C)>;
+        constexpr auto K = &pt_split_kernel<KV(NN), KV(C), false, true>;
+        int nb = 0;
+        if (allow_dyn_lds<K>(L::LDS) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K, SP_NT, L::LDS) != hipSuccess)
+            return 0;
+        return nb;
+    });
 }
 
 bool split_supported(int N2, int CHI, int n_traj, int n_cu, bool ow) {
-    return (CHI == 16 || CHI == 32 || CHI == 64) &&
-           (N2 == 4 || N2 == 9 || N2 == 16 || N2 == 25 || N2 == 36) && n_traj >= 1 &&
-           (long long)n_traj * split_group_size(N2, ow) <= n_cu;
+    return split_instance(N2, CHI) && n_traj >= 1 && (long long)n_traj * split_group_size(N2, ow) <= n_cu;
 }
 
 // X: n_traj * 4 * N2 * CHI double2 exchange buffer (granules, tags zeroed here); cnt: n_traj * 64 arrival words and err,
@@ -694,14 +624,7 @@ hipError_t launch_split(int N2, int CHI, int n_traj, const SweepParams& p, doubl
         SweepParams q = p;
         q.traj_base = base;
         const int n = n_traj - base < chunk ? n_traj - base : chunk;
-        switch (N2) {
-            case 4: e = launch_split_n<4>(CHI, n, q, X, cnt, err, s); break;
-            case 9: e = launch_split_n<9>(CHI, n, q, X, cnt, err, s); break;
-            case 16: e = launch_split_n<16>(CHI, n, q, X, cnt, err, s); break;
-            case 25: e = launch_split_n<25>(CHI, n, q, X, cnt, err, s); break;
-            case 36: e = launch_split_n<36>(CHI, n, q, X, cnt, err, s); break;
-            default: return hipErrorInvalidValue;
-        }
+        e = split_dispatch(N2, CHI, [&](auto NN, auto C) { return launch_split_t<KV(NN), KV(C)>(n, q, X, cnt, err, s); });
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -1426,85 +1426,57 @@ hipError_t launch_sw(int n_blocks, const SweepParams& p, hipStream_t s) {
     constexpr size_t LDS = L::LDS + (LEAN ? LeanStage<BT * L::TS + BT * N2>::BYTES : 0);
     static_assert((BT * L::TS + BT * N2) * sizeof(double2) == L::LDS, "the area starts where the states and rbuf end");
     static_assert(LDS + 512 <= 160 * 1024, "LDS budget (512 B: the kernel's static tables)");
-    static unsigned attr = 0;  // per-device bitmask (the attribute belongs to the device's copy of the kernel)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    if (dev >= 32 || !(attr & (1u << dev))) {
-        hipError_t e = hipFuncSetAttribute((const void*)pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) return e;
-        if (dev < 32) attr |= 1u << dev;
-    }
+    if (hipError_t e = allow_dyn_lds<&pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN>>(LDS); e != hipSuccess) return e;
     hipLaunchKernelGGL((pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN>), dim3(n_blocks), dim3(64 * L::NW), LDS, s, p, p.M,
                        p.Q, p.out, p.F, p.W);
     return hipGetLastError();
 }
 
+// the instance set: BT = 8 trajectories per workgroup fit the LDS up to N2 = 16, and chi = 128 keeps 4 augmented
+// states of N2 <= 16 there (132 KiB); larger N2 or BT do not fit
+constexpr int sw_max_bt(int N2) { return N2 <= 16 ? 8 : 4; }
+constexpr bool sw_instance(int N2, int CHI, int BT) {
+    return n2_listed(N2) && (BT == 4 || (BT == 8 && sw_max_bt(N2) == 8)) &&
+           (CHI == 16 || CHI == 32 || CHI == 64 || (CHI == 128 && BT == 4 && N2 <= 16));
+}
+
 template <int N2, int BT, bool TRUNK = false>
 hipError_t launch_sw_chi(int CHI, int n_blocks, const SweepParams& p, hipStream_t s) {
-    switch (CHI) {
-        case 16: return launch_sw<N2, 16, BT, TRUNK>(n_blocks, p, s);
-        case 32: return launch_sw<N2, 32, BT, TRUNK>(n_blocks, p, s);
-        case 64: return launch_sw<N2, 64, BT, TRUNK>(n_blocks, p, s);
-        case 128:
-            // chi = 128 keeps 4 augmented states of N2 <= 16 in LDS (132 KiB); larger N2 or BT do not fit
-            if constexpr (BT == 4 && N2 <= 16) return launch_sw<N2, 128, BT, TRUNK>(n_blocks, p, s);
-            return hipErrorInvalidValue;
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_list<16, 32, 64, 128>(CHI, [&](auto C) -> hipError_t {
+        if constexpr (sw_instance(N2, KV(C), BT)) return launch_sw<N2, KV(C), BT, TRUNK>(n_blocks, p, s);
+        else return hipErrorInvalidValue;
+    });
 }
 
 }  // namespace
 
-bool sweep_supported(int N2, int CHI) {
-    return (N2 == 4 || N2 == 9 || N2 == 16 || N2 == 25 || N2 == 36) &&
-           (CHI == 1 || CHI == 16 || CHI == 32 || CHI == 64 || (CHI == 128 && N2 <= 16));
-}
+// (chi = 1: the kernel without a PT, launch_sweep_nopt)
+bool sweep_supported(int N2, int CHI) { return n2_listed(N2) && (CHI == 1 || sw_instance(N2, CHI, 4)); }
 
 // trajectories per workgroup that fit the LDS for this N2 (8 halves the per-trajectory PT-slice traffic)
-int sweep_max_bt(int N2) { return N2 <= 16 ? 8 : 4; }
+int sweep_max_bt(int N2) { return sw_max_bt(N2); }
 
 hipError_t launch_sweep(int N2, int CHI, int BT, int n_blocks, const SweepParams& p, hipStream_t s) {
     if (n_blocks <= 0) return hipSuccess;
-    if (p.ck_map) {  // trunk pre-pass: four trunks per workgroup
-        if (BT != 4) return hipErrorInvalidValue;
-        switch (N2) {
-            case 4: return launch_sw_chi<4, 4, true>(CHI, n_blocks, p, s);
-            case 9: return launch_sw_chi<9, 4, true>(CHI, n_blocks, p, s);
-            case 16: return launch_sw_chi<16, 4, true>(CHI, n_blocks, p, s);
-            case 25: return launch_sw_chi<25, 4, true>(CHI, n_blocks, p, s);
-            case 36: return launch_sw_chi<36, 4, true>(CHI, n_blocks, p, s);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    if (BT == 8) {
-        switch (N2) {
-            case 4: return launch_sw_chi<4, 8>(CHI, n_blocks, p, s);
-            case 9: return launch_sw_chi<9, 8>(CHI, n_blocks, p, s);
-            case 16:
+    if (BT != 4 && (BT != 8 || p.ck_map)) return hipErrorInvalidValue;
+    return dispatch_n2(N2, [&](auto NN) -> hipError_t {
+        constexpr int N = KV(NN);
+        if (p.ck_map) return launch_sw_chi<N, 4, true>(CHI, n_blocks, p, s);  // trunk pre-pass: four trunks per workgroup
+        if (BT == 4) return launch_sw_chi<N, 4>(CHI, n_blocks, p, s);
+        if constexpr (sw_max_bt(N) == 8) {
+            if constexpr (N == 16) {
                 if (p.lean && CHI == 64) return launch_sw<16, 64, 8, false, true>(n_blocks, p, s);
-                return launch_sw_chi<16, 8>(CHI, n_blocks, p, s);
-            default: return hipErrorInvalidValue;
+            }
+            return launch_sw_chi<N, 8>(CHI, n_blocks, p, s);
         }
-    }
-    if (BT != 4) return hipErrorInvalidValue;
-    switch (N2) {
-        case 4: return launch_sw_chi<4, 4>(CHI, n_blocks, p, s);
-        case 9: return launch_sw_chi<9, 4>(CHI, n_blocks, p, s);
-        case 16: return launch_sw_chi<16, 4>(CHI, n_blocks, p, s);
-        case 25: return launch_sw_chi<25, 4>(CHI, n_blocks, p, s);
-        case 36: return launch_sw_chi<36, 4>(CHI, n_blocks, p, s);
-        default: return hipErrorInvalidValue;
-    }
+        return hipErrorInvalidValue;
+    });
 }
 
 hipError_t launch_sweep_nopt(int N2, int n_traj, const SweepParams& p, hipStream_t s) {
     if (n_traj <= 0) return hipSuccess;
-#define PQD_NOPT(NN) case NN: hipLaunchKernelGGL(sweep_nopt_kernel<NN>, dim3(n_traj), dim3(64), 0, s, p); break;
-    switch (N2) {
-        PQD_NOPT(4) PQD_NOPT(9) PQD_NOPT(16) PQD_NOPT(25) PQD_NOPT(36)
-        default: return hipErrorInvalidValue;
-    }
-#undef PQD_NOPT
-    return hipGetLastError();
+    return dispatch_n2(N2, [&](auto NN) {
+        hipLaunchKernelGGL(sweep_nopt_kernel<KV(NN)>, dim3(n_traj), dim3(64), 0, s, p);
+        return hipGetLastError();
+    });
 }

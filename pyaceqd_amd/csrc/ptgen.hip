@@ -1617,7 +1617,8 @@ decltype(auto) dispatch_pow2(int v, F&& f) {
         return dispatch_pow2<Vs...>(v, std::forward<F>(f));
     }
 }
-#define KV(E) decltype(E)::value  // the constant a dispatch_pow2 lambda was called with
+// (KV(E), the constant a dispatch lambda was called with, and dispatch_list, which answers an unlisted value with an
+// error instead, are in pqd_common.h)
 
 // Every PQD_PTG_* switch the two entry points read (A/B runs and tests; INTEGRATION.md "Runtime switches", in that
 // order, then the timing-only PQD_PTG_DIAG). read_ptg_env() is the only place this file reads the environment. It runs once per

@@ -311,9 +311,7 @@ static_assert((size_t)2 * 16 * (TW_B8_NMAX | 1) * sizeof(double2) + 64 <= 160 * 
 
 template <int B>
 hipError_t tw_prepare(size_t lds, int* per_cu) {
-    // per call, as the other launchers do: the attribute belongs to the current device
-    hipError_t e0 = hipFuncSetAttribute((const void*)tl_dynmap_wide_kernel<B>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - 64));
+    hipError_t e0 = allow_dyn_lds<&tl_dynmap_wide_kernel<B>>(160 * 1024 - 64);
     if (e0 != hipSuccess) return e0;
     int nb = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, tl_dynmap_wide_kernel<B>, TW_THREADS, lds);

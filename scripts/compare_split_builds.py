@@ -1,0 +1,204 @@
+"""Bit-for-bit comparison of the PT propagation paths between two libpqd builds.
+
+usage: python scripts/compare_split_builds.py LIB_A LIB_B [--only SUBSTRING[,SUBSTRING...]] [--log FILE]
+
+For every case one child process per library (one after the other, each under its own time limit, the library chosen
+through PQD_LIB, the case's switches in its environment) runs a plan on seeded inputs and saves every trajectory's
+outputs, the plan's path, its fallback count and pqd_plan_describe's text; the parent compares every array with
+np.array_equal and the texts as strings. Inputs are built like tests/test_gpu_parity.py::test_sweep_pt_split_groups and
+tests/test_gpu_msplit.py: three systems, ragged windows, MTOs before and after an output (at step 0 and at a window's
+last step among them), 150 steps, and a schedule that changes the slice at most steps and repeats it at some, so the
+split kernels' schedule reader crosses its 64-entry chunk boundary twice. The cases together run every instance of
+pt_split_kernel and pt_msplit_kernel (named in the case id), their switches, and one case per N2 of the batched sweep,
+the quad kernel and the free propagators (the launch layer's dispatch). Exit status 0: all equal; 1: a difference;
+2: a child failed (the run stops there: nothing more is started on the device)."""
+import argparse
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, HERE)
+
+N_STEPS = 150
+SWITCHES = ("PQD_SPLIT", "PQD_SPLIT_GRAN", "PQD_SPLIT_OW", "PQD_SPLIT_XCD", "PQD_SPLIT_L2", "PQD_SPLIT_SPIN",
+            "PQD_MSPLIT", "PQD_MS_L2", "PQD_MS_PTM", "PQD_MS_TB", "PQD_ABLATE", "PQD_FPM", "PQD_QUAD")
+SPLIT, MSPLIT = "split groups", "split groups, several trajectories per group"
+BATCHED, QUAD = "batched lock-step sweep", "register-resident TLS quads"
+
+
+def _cases():
+    """id -> (kind, parameters, switches, expected path or None)"""
+    c = {}
+    modes = {"granule": {"PQD_SPLIT_GRAN": 1}, "counter_ow": {"PQD_SPLIT_OW": 1}, "counter_noow": {"PQD_SPLIT_OW": 0}}
+    for N in (2, 3, 4, 5, 6):
+        for chi in (16, 32, 64):
+            for tag, env in modes.items():
+                c[f"split_N2={N * N}_chi={chi}_{tag}"] = ("pt", dict(N=N, chi=chi), dict(PQD_SPLIT=2, **env), SPLIT)
+    for chi, Ns in ((32, (3, 4, 5, 6)), (64, (3, 4, 6)), (128, (3, 4)), (256, (2, 3, 4))):
+        for N in Ns:
+            c[f"msplit_N2={N * N}_chi={chi}"] = ("pt", dict(N=N, chi=chi, n_traj=7), dict(PQD_MSPLIT=2), MSPLIT)
+    sp = dict(N=4, chi=64)
+    ms = dict(N=4, chi=64, n_traj=19)
+    c["split_N2=16_chi=64_noxcd"] = ("pt", sp, dict(PQD_SPLIT=2, PQD_SPLIT_XCD=0), SPLIT)
+    c["msplit_N2=16_chi=64_noxcd"] = ("pt", ms, dict(PQD_MSPLIT=2, PQD_SPLIT_XCD=0), MSPLIT)
+    c["split_N2=16_chi=64_l2=0"] = ("pt", sp, dict(PQD_SPLIT=2, PQD_SPLIT_L2=0), SPLIT)
+    c["msplit_N2=16_chi=64_l2=0"] = ("pt", ms, dict(PQD_MSPLIT=2, PQD_MS_L2=0), MSPLIT)
+    # a placement miss: the split plan falls back to the batched kernel, the msplit plan re-runs with sc1 stores
+    c["split_N2=16_chi=64_ablate=512"] = ("pt", sp, dict(PQD_SPLIT=2, PQD_ABLATE=512), BATCHED)
+    c["msplit_N2=16_chi=64_ablate=512"] = ("pt", ms, dict(PQD_MSPLIT=2, PQD_ABLATE=512), MSPLIT)
+    # every wait times out: both fall back to the batched kernel
+    c["split_N2=16_chi=64_spin=0"] = ("pt", sp, dict(PQD_SPLIT=2, PQD_SPLIT_SPIN=0), BATCHED)
+    c["msplit_N2=16_chi=64_spin=0"] = ("pt", ms, dict(PQD_MSPLIT=2, PQD_SPLIT_SPIN=0), BATCHED)
+    for ptm in (0, 1):
+        c[f"msplit_N2=16_chi=64_ptm={ptm}"] = ("pt", ms, dict(PQD_MSPLIT=2, PQD_MS_PTM=ptm), MSPLIT)
+    for tb in (1, 3, 5):
+        c[f"msplit_N2=16_chi=64_tb={tb}"] = ("pt", ms, dict(PQD_MSPLIT=2, PQD_MS_TB=tb), MSPLIT)
+    # G = 37 > 32: the single-counter branch (also split_N2=36_* above)
+    c["split_N2=36_chi=32_single_counter"] = ("pt", dict(N=6, chi=32, n_traj=3), dict(PQD_SPLIT=2), SPLIT)
+    # a batch above the co-resident capacity: split_chunk consecutive launches (auto mode)
+    c["split_N2=9_chi=16_consecutive_launches"] = ("pt", dict(N=3, chi=16, n_traj=256 // 9 + 2), {}, SPLIT)
+    for N in (2, 3, 4, 5, 6):
+        # (PQD_QUAD=0: the two-level system on the batched kernel too)
+        c[f"sweep_N2={N * N}_chi=32"] = ("pt", dict(N=N, chi=32, n_traj=9), dict(PQD_SPLIT=0, PQD_QUAD=0), BATCHED)
+        c[f"free_N2={N * N}"] = ("free", dict(N=N), {}, None)
+        c[f"free_N2={N * N}_fpm=0"] = ("free", dict(N=N), dict(PQD_FPM=0), None)
+    for chi in (16, 32, 64):
+        c[f"quad_N2=4_chi={chi}"] = ("pt", dict(N=2, chi=chi, n_traj=9), dict(PQD_SPLIT=0, PQD_QUAD=2), QUAD)
+    return c
+
+
+def _trajectories(N, n_traj, seed):
+    """ragged windows and ends; MTOs of kinds 0/1/2 at step 0, mid-run and at the window's last step, before and after
+    at one step, two in one slot, and trajectories without any (tests/test_gpu_msplit.py mixed_trajectories)"""
+    from pyaceqd_amd.engine import MTO, Trajectories
+    rng = np.random.default_rng(seed)
+    beg, end, mt = [], [], []
+    for t in range(n_traj):
+        e = int(rng.integers(N_STEPS // 2, N_STEPS + 1))
+        if t == 0:
+            e = N_STEPS  # one trajectory reads the whole schedule
+        b = int(rng.integers(0, e))
+        beg.append(b)
+        end.append(e)
+        A = rng.normal(size=(N, N)) + 1j * rng.normal(size=(N, N))
+        B = rng.normal(size=(N, N)) + 1j * rng.normal(size=(N, N))
+        A, B = A / np.linalg.norm(A), B / np.linalg.norm(B)
+        s = int(rng.integers(0, e + 1))
+        k = t % 6
+        if k == 0:
+            mt += [MTO(t, s, False, 2, A), MTO(t, s, False, 1, B)]
+        elif k == 1:
+            mt += [MTO(t, 0, True, 0, A)]
+        elif k == 2:
+            mt += [MTO(t, s, True, 1, A), MTO(t, s, False, 2, B)]
+        elif k == 3:
+            mt += [MTO(t, e, False, 0, A), MTO(t, max(0, e - 3), True, 2, B)]
+        elif k == 4:
+            mt += [MTO(t, s, False, 0, A), MTO(t, min(e, s + 1), False, 1, np.eye(N) * 0.5 + B)]
+    return Trajectories(np.array(beg), np.array(end), mt)
+
+
+def _schedule(n_slices, seed):
+    """a new slice at about four steps of five, the same slice again at the others"""
+    rng = np.random.default_rng(seed)
+    s = np.zeros(N_STEPS, dtype=np.int32)
+    for n in range(1, N_STEPS):
+        s[n] = s[n - 1] if rng.random() < 0.2 else (s[n - 1] + 1 + rng.integers(0, n_slices - 1)) % n_slices
+    return s
+
+
+def _child(case, out):
+    kind, p, _, want = _cases()[case]
+    from pyaceqd_amd import engine, pt as ptmod
+    from pyaceqd_amd.engine import Grid
+    from tests import helpers as H
+    N = p["N"]
+    res = {}
+    if kind == "free":
+        sysd, grid = H.random_system(N, n_steps=12, n_sub=2, dt=1.0, seed=7 * N)
+        res["M"] = engine.free_propagators(sysd, grid)
+    else:
+        chi = p["chi"]
+        n_traj = p.get("n_traj", max(1, min(7, 256 // (N * N + 1))))  # every group resident
+        systems = [H.random_system(N, n_steps=N_STEPS, seed=40 + k)[0] for k in range(3)]
+        grid = Grid(0.0, 0.1, N_STEPS)
+        tr = _trajectories(N, n_traj, seed=N + chi)
+        tr.system = np.array([k % 3 for k in range(n_traj)])
+        pt = ptmod.random_pt(N, chi, D=min(N * N, 9), n_slices=9, seed=chi + N, eps=0.05)
+        sched = _schedule(9, seed=chi + 7 * N)
+        pt.schedule = lambda n_steps: np.ascontiguousarray(sched[:n_steps])
+        ops = [H.ketbra(N, 0, 0), H.ketbra(N, 1, 0), np.eye(N)]
+        plan = engine.Plan(systems, grid, H.random_rho(N), ops, tr, pt=pt)
+        desc = " ".join(f"{k}={v}" for k, v in sorted(plan.describe().items()))
+        plan.execute()
+        for t, a in enumerate(plan.download()):
+            res[f"out{t:03d}"] = a
+        path, bt, fb = plan.info()
+        if want is not None and path != want:
+            raise SystemExit(f"{case}: ran on '{path}', not on '{want}'")
+        res["info"] = np.array(f"path={path} bt={bt} split_fallbacks={fb}")
+        res["describe"] = np.array(desc)
+    np.savez(out, **res)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("libs", nargs="*")
+    ap.add_argument("--only", default="")
+    ap.add_argument("--log", default="")
+    ap.add_argument("--child", default="")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    if a.child:
+        return _child(a.child, a.out)
+    if len(a.libs) != 2:
+        ap.error("two library paths")
+    libs = [os.path.abspath(x) for x in a.libs]
+    log = open(a.log, "w") if a.log else None
+
+    def say(line):
+        print(line, flush=True)
+        if log:
+            log.write(line + "\n")
+            log.flush()
+
+    say(f"# A = {a.libs[0]}  B = {a.libs[1]}; one child process per case and library; np.array_equal on every output, "
+        "the plan's path, fallbacks and description as text")
+    n_diff = 0
+    cases = {k: v for k, v in _cases().items() if any(t in k for t in a.only.split(","))}
+    with tempfile.TemporaryDirectory() as tmp:
+        for cid, (_, _, sw, _) in cases.items():
+            got = []
+            for i, lib in enumerate(libs):
+                env = {k: v for k, v in os.environ.items() if k not in SWITCHES}
+                env["PQD_LIB"] = lib
+                assert all(k in SWITCHES for k in sw)
+                env.update({k: str(v) for k, v in sw.items()})
+                out = os.path.join(tmp, f"{i}.npz")
+                try:
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", cid, "--out", out],
+                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+                except subprocess.TimeoutExpired:
+                    say(f"CHILD TIMED OUT {cid} lib {'AB'[i]}")
+                    return 2
+                if r.returncode != 0:
+                    say(f"CHILD FAILED {cid} lib {'AB'[i]} exit {r.returncode}\n{r.stdout[-2000:]}")
+                    return 2
+                with np.load(out) as z:
+                    got.append({k: z[k] for k in z.files})
+            A, B = got
+            bad = [k for k in sorted(set(A) | set(B))
+                   if k not in A or k not in B or A[k].shape != B[k].shape or not np.array_equal(A[k], B[k])]
+            n_diff += bool(bad)
+            what = str(A["info"]) if "info" in A else f"M{tuple(A['M'].shape)}"
+            say(f"{'DIFFER ' + ','.join(bad) if bad else 'equal '} {cid}  [{len(A)} arrays; {what}]")
+    say(f"# {len(cases)} cases, {n_diff} differ")
+    return 1 if n_diff else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -260,6 +260,36 @@ def test_msplit_chi256_vs_oracle(N, n_traj, chi):
     cmp_lists(got, oracle.propagate(systems, grid, rho0, ops, tr, pt=pt, nthreads=8), 1e-11)
 
 
+@pytest.mark.parametrize("path,N,chi,env", [
+    ("split groups", 2, 16, {"PQD_SPLIT": "2"}),
+    ("split groups", 3, 16, {"PQD_SPLIT": "2"}),
+    (MSPLIT, 3, 32, {"PQD_MSPLIT": "2", "PQD_MS_TB": "3"}),
+])
+def test_split_groups_read_the_schedule_past_its_first_chunks(monkeypatch, path, N, chi, env):
+    """150 steps with a schedule that changes the slice at every step (period 9, n_init = 0): both split-group kernels
+    keep the schedule in 64-entry register chunks (split_handoff.h sched_chunk) and refill them at steps 64 and 128,
+    which the 30- and 40-step cases above never reach; ragged windows, MTOs and three systems as there, vs the oracle"""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    n_steps, n_sys, n_traj = 150, 3, 7
+    systems = [H.random_system(N, n_steps=n_steps, seed=30 + k)[0] for k in range(n_sys)]
+    grid = Grid(0.0, 0.1, n_steps)
+    tr = mixed_trajectories(n_steps, N, n_traj, seed=N + chi)
+    tr.out_end[0] = n_steps  # one trajectory runs through every chunk
+    tr.system = np.array([k % n_sys for k in range(n_traj)])
+    pt = ptmod.random_pt(N, chi, D=min(N * N, 9), n_slices=9, seed=chi + N, eps=0.05)
+    pt.n_init = 0
+    sched = pt.schedule(n_steps)
+    assert np.all(sched[1:] != sched[:-1]) and len(set(sched.tolist())) == 9
+    ops = [H.ketbra(N, 0, 0), H.ketbra(N, 1, 0), np.eye(N)]
+    rho0 = H.random_rho(N)
+    plan = engine.Plan(systems, grid, rho0, ops, tr, pt=pt)
+    plan.execute()
+    got = plan.download()
+    assert plan.info()[0] == path and plan.info()[2] == 0
+    cmp_lists(got, oracle.propagate(systems, grid, rho0, ops, tr, pt=pt, nthreads=8), 1e-11)
+
+
 def test_chi256_batch_beyond_one_launch_is_refused():
     """chi = 256 has no batched fallback: a batch the groups cannot hold in one launch is refused at plan creation"""
     N = 4
