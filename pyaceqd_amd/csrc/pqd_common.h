@@ -452,7 +452,7 @@ constexpr int sweep_rmax(int N2, int BT, int CHI) {
 hipError_t launch_sweep(int N2, int CHI, int BT, int n_blocks, const SweepParams& p, hipStream_t s);
 int sweep_max_bt(int N2);
 hipError_t launch_sweep_nopt(int N2, int n_blocks, const SweepParams& p, hipStream_t s);
-hipError_t launch_mapchain(const MapChainParams& p, hipStream_t s);
+hipError_t launch_mapchain(const MapChainParams& p, bool pipe, hipStream_t s);  // pipe: the pipelined tau kernel
 hipError_t launch_mapchain_blocked(const MapChainParams& p, int n_chain, hipStream_t s);
 hipError_t launch_four_time(const FourTimeParams& p, hipStream_t s);
 hipError_t launch_propagate_tau(int N2, const double2* dm, const double2* rho0, int n_tau, int j_start,

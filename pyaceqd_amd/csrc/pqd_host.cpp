@@ -2327,149 +2327,147 @@ int pqd_fail_msg(int code, const char* msg) { return fail(code, "%s", msg); }
 // =================================================================================================
 // map-chain sweeps
 // =================================================================================================
-static int mapchain_run(pqd_ctx* ctx, MapChainParams& p, const pqd_c128* dmA, size_t nA, const pqd_c128* dmB,
-                        size_t nB, const pqd_c128* dmT, size_t nT, const pqd_c128* dm_s, const pqd_c128* rho_init,
-                        const pqd_c128* opA, const pqd_c128* opB, const pqd_c128* opC, const double* time,
-                        const double* time_sparse, pqd_c128* result) {
-    if (!ctx || !rho_init || !opA || !opB || !opC || !time || !time_sparse || !result || !dmA)
-        return fail(PQD_ERR_ARG, "NULL argument");
-    if (p.dim < 2 || p.dim > 6) return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [2, 6]", p.dim);
-    if (p.n_t < 1 || p.n_tfull < 1 || p.n_tau < 0) return fail(PQD_ERR_ARG, "bad sizes");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const int N2 = p.dim * p.dim;
-    p.N2 = N2;
-    const size_t m2 = (size_t)N2 * N2;
-    const size_t nres = (size_t)p.n_t * (p.n_tau + 1);
-    // calc_onetime_parallel on the blocked sweep (mapchain.hip): the trunk ends j_i are found here with the
-    // Fortran's own comparisons (propagate_tau.f90:144-151), which also bounds every map the sweep reads
-    const char* eb = getenv("PQD_MC_BLOCKED");
-    bool blocked = (p.mode == 0 || p.mode == 1) && !(eb && atoi(eb) == 0) &&
-                   (N2 == 4 || N2 == 9 || N2 == 16 || N2 == 25 || N2 == 36);
-    std::vector<int> pos;
-    int pmax = 0;
-    if (p.mode == 0 || blocked) {
-        pos.resize(p.n_t);
-        int j = 1;
-        for (int i = 0; i < p.n_t; ++i) {
-            while (j <= p.n_tfull && time[j - 1] < time_sparse[i]) ++j;
-            pos[i] = j - 1;
-            pmax = std::max(pmax, j - 1);
-        }
+// dims of the map-chain, propagate_tau and four-time entry points: one trajectory's Liouville vector fits a wave
+static bool check_dim_2_6(int dim) { return dim >= 2 && dim <= 6; }
+
+// The PQD_MC_* switches (in that order), read once per call: tests flip them between calls.
+struct McEnv { bool blocked, pipe, timing; int L; };
+static McEnv read_mc_env() {
+    auto num = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+    McEnv v;
+    v.blocked = num("PQD_MC_BLOCKED", 1) != 0;  // modes 0 and 1 on the blocked sweep (0: map by map)
+    v.L = num("PQD_MC_L", INT_MIN);             // its block length (raw value; INT_MIN: unset, sqrt(n_tau))
+    v.pipe = num("PQD_MC_PIPE", 1) != 0;        // map-by-map tau sweep with the register pipeline (0: mc_tau_kernel)
+    v.timing = getenv("PQD_MC_TIMING") != nullptr;  // host-side phase times of the call on stderr
+    return v;
+}
+
+struct McIn {  // the host arrays of one map-chain call (nA, nB, nT maps in dmA, dmB, dmT)
+    const pqd_c128 *dmA, *dmB, *dmT, *dm_s, *rho_init, *opA, *opB, *opC;
+    size_t nA, nB, nT;
+    const double *time, *time_sparse;
+};
+
+// the trunk ends pos[i] = j_i - 1 with the Fortran's own comparisons (propagate_tau.f90:144-151); never decreasing
+static std::vector<int> trunk_positions(const MapChainParams& p, const McIn& in) {
+    std::vector<int> pos(p.n_t);
+    for (int i = 0, j = 1; i < p.n_t; ++i) {
+        while (j <= p.n_tfull && in.time[j - 1] < in.time_sparse[i]) ++j;
+        pos[i] = j - 1;
     }
-    // mode 0 reads dm_tl(:, :, j_i - 1 + n_tau) at its last tau step on either set of kernels
-    if (p.mode == 0 && (size_t)std::max(Q_of(pos, p.n_tau), pmax) > nA)
+    return pos;
+}
+
+// Blocked sweep (mapchain.hip) or map by map: sets `blocked`, and for the blocked sweep pos, p.q_s, p.L, p.Q, p.n_blk
+static int choose_blocked(MapChainParams& p, const McEnv& env, const McIn& in, bool& blocked, std::vector<int>& pos) {
+    blocked = (p.mode == 0 || p.mode == 1) && env.blocked && n2_listed(p.N2);
+    if (p.mode == 0 || blocked) pos = trunk_positions(p, in);
+    // mode 0 reads dm_tl(:, :, j_i - 1 + n_tau) at its last tau step, on either set of kernels
+    if (p.mode == 0 && (size_t)Q_of(pos, p.n_tau) > in.nA)
         return fail(PQD_ERR_ARG, "the sweep would read map %d of %zu (time_sparse beyond time, or n_tau too long "
-                    "for dm_tl)", std::max(Q_of(pos, p.n_tau), pmax), nA);
+                    "for dm_tl)", Q_of(pos, p.n_tau), in.nA);
     if (blocked && p.mode == 1) {
-        // a trunk that ends past the first period (j > n_tb) never wraps in the tau loop (:270-287: jj resets
-        // only when it equals n_tb + 1), so that trajectory applies dm_s at every tau step: it starts at q_s, the
-        // first position of a constant dm_s region placed after the periodic positions (map_at)
-        int qp = 0;
-        bool any_s = false;
+        // a trunk that ends past the first period (j > n_tb) never wraps in the tau loop (:270-287: jj resets only at
+        // n_tb + 1) and applies dm_s at every tau step: it starts at q_s, where a constant dm_s region begins (map_at)
+        int qp = 0, any_s = 0;
         for (int i = 0; i < p.n_t; ++i) {
             if (pos[i] + 1 <= p.n_tb) qp = std::max(qp, pos[i] + p.n_tau);
-            else any_s = true;
+            else any_s = 1;
         }
         p.q_s = any_s ? qp : INT_MAX;
         for (int i = 0; i < p.n_t; ++i)
             if (pos[i] + 1 > p.n_tb) pos[i] = p.q_s;
-        // precondition of that constant region: with n_map > n_tb a trunk ending at n_tb < j <= n_map walks
-        // dm_block(j), dm_block(j+1), ..., dm_block(n_map) before dm_s (:270-281), which the blocked position
-        // map does not represent; such calls run on the map-by-map kernels
+        // precondition of that region: with n_map > n_tb a trunk ending at n_tb < j <= n_map walks dm_block(j ..
+        // n_map) before dm_s (:270-281), which map_at does not represent; such calls run on the map-by-map kernels
         if (any_s && p.n_map > p.n_tb) blocked = false;
     }
     if (blocked) {
-        const int Q = Q_of(pos, p.n_tau);
-        const char* el = getenv("PQD_MC_L");
-        int L = el ? atoi(el) : (int)std::lround(std::sqrt((double)std::max(1, p.n_tau)));
-        L = std::max(8, std::min(256, L));
-        p.L = L;
-        p.Q = std::max(Q, 1);
-        p.n_blk = (p.Q + L - 1) / L;
+        const int L = env.L != INT_MIN ? env.L : (int)std::lround(std::sqrt((double)std::max(1, p.n_tau)));
+        p.L = std::max(8, std::min(256, L));
+        p.Q = std::max(Q_of(pos, p.n_tau), 1);
+        p.n_blk = (p.Q + p.L - 1) / p.L;
     }
+    return PQD_OK;
+}
+
+// the caller's result array is typically fresh (f2py-style: np.zeros, pages not yet mapped): its pages are faulted
+// in on a few host threads while the maps upload and the kernels run, so the copy back runs at the link rate (a
+// 41 MB copy into fresh pages: 1.7 ms, into mapped ones 0.73 ms; scripts/ubench_h2d.py). Without a thread the
+// copy back is only slower: nothing is thrown.
+struct PageToucher {
+    std::thread t;
+    PageToucher(void* buf, size_t bytes) { try { t = std::thread(touch_pages, buf, bytes); } catch (...) {} }
+    ~PageToucher() { if (t.joinable()) t.join(); }
+};
+
+// PQD_MC_TIMING: host-side phase times of the call on stderr (diagnostics)
+static void print_mc_timing(const std::chrono::steady_clock::time_point (&t)[5]) {
+    auto ms = [&](int a, int b) { return std::chrono::duration<double, std::milli>(t[b] - t[a]).count(); };
+    fprintf(stderr, "pqd mapchain: upload+launch %.3f ms, page touch left %.3f ms, kernels left %.3f ms, download %.3f ms\n",
+            ms(0, 1), ms(1, 2), ms(2, 3), ms(3, 4));
+}
+
+static int mapchain_run(pqd_ctx* ctx, MapChainParams& p, const McIn& in, pqd_c128* result) {
+    if (!ctx || !in.rho_init || !in.opA || !in.opB || !in.opC || !in.time || !in.time_sparse || !result || !in.dmA)
+        return fail(PQD_ERR_ARG, "NULL argument");
+    if (!check_dim_2_6(p.dim)) return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [2, 6]", p.dim);
+    if (p.n_t < 1 || p.n_tfull < 1 || p.n_tau < 0) return fail(PQD_ERR_ARG, "bad sizes");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    p.N2 = p.dim * p.dim;
+    const size_t nres = (size_t)p.n_t * (p.n_tau + 1);
+    const McEnv env = read_mc_env();
+    bool blocked;
+    std::vector<int> pos;
+    if (int rc = choose_blocked(p, env, in, blocked, pos)) return rc;
     // every device buffer of the call carved from the context's arena
+    const size_t N2 = p.N2, m2 = N2 * N2;
     auto carve = [&](Carve& c) {
-        p.dmA = c.take<double2>(nA * m2);
-        p.dmB = dmB ? c.take<double2>(nB * m2) : nullptr;
-        p.dmT = dmT ? c.take<double2>(nT * m2) : nullptr;
-        p.dm_s = dm_s ? c.take<double2>(m2) : nullptr;
-        p.rho_init = c.take<double2>(N2);
-        p.opA = c.take<double2>(N2);
-        p.opB = c.take<double2>(N2);
-        p.opC = c.take<double2>(N2);
-        p.time = c.take<double>(p.n_tfull);
-        p.time_sparse = c.take<double>(p.n_t);
-        p.rho_buf = c.take<double2>((size_t)p.n_t * N2);
-        p.j_arr = c.take<int>(p.n_t);
-        p.result = c.take<double2>(nres);
-        if (blocked) {
-            p.pos = c.take<int>(p.n_t);
-            p.U = c.take<double2>((size_t)p.Q * N2);
-            p.Rend = c.take<double2>((size_t)p.n_blk * m2);
-            p.P = c.take<double2>((size_t)(p.n_blk + 1) * N2);
-            p.X = c.take<double2>((size_t)p.n_blk * p.n_t * N2);
-        }
+        p.dmA = c.take<double2>(in.nA * m2);
+        p.dmB = in.dmB ? c.take<double2>(in.nB * m2) : nullptr;
+        p.dmT = in.dmT ? c.take<double2>(in.nT * m2) : nullptr;
+        p.dm_s = in.dm_s ? c.take<double2>(m2) : nullptr;
+        p.rho_init = c.take<double2>(N2); p.opA = c.take<double2>(N2); p.opB = c.take<double2>(N2); p.opC = c.take<double2>(N2);
+        p.time = c.take<double>(p.n_tfull); p.time_sparse = c.take<double>(p.n_t);
+        p.rho_buf = c.take<double2>(p.n_t * N2); p.j_arr = c.take<int>(p.n_t); p.result = c.take<double2>(nres);
+        if (!blocked) return;
+        p.pos = c.take<int>(p.n_t); p.U = c.take<double2>(p.Q * N2); p.Rend = c.take<double2>(p.n_blk * m2);
+        p.P = c.take<double2>((p.n_blk + 1) * N2); p.X = c.take<double2>((size_t)p.n_blk * p.n_t * N2);
     };
-    Carve sz;
+    Carve sz, cv;
     carve(sz);
     if (ctx->mc_arena.n < sz.off + 256) {
         HIPCHK(hipStreamSynchronize(s));
         HIPCHK(ctx->mc_arena.alloc(sz.off + sz.off / 4 + 256));
     }
-    Carve cv;
     cv.base = ctx->mc_arena.p;
     carve(cv);
-    auto up = [&](const void* dst, const void* src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(const_cast<void*>(dst), src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    // PQD_MC_TIMING=1: host-side phase times of this call on stderr (diagnostics)
-    const bool tmg = getenv("PQD_MC_TIMING") != nullptr;
     auto now = [] { return std::chrono::steady_clock::now(); };
-    const auto t0 = now();
-    // the caller's result array is typically fresh (f2py-style: np.zeros, pages not yet mapped): fault its pages in
-    // on a few host threads while the maps upload and the kernels run, so the copy back runs at the link rate (a
-    // 41 MB copy into fresh pages: 1.7 ms, into mapped ones 0.73 ms; scripts/ubench_h2d.py)
-    std::thread toucher;
-    try {
-        toucher = std::thread(touch_pages, (void*)result, nres * sizeof(double2));
-    } catch (...) {  // thread creation failed: skip the pre-touch (the copy back is only slower), never throw
-    }
-    struct Join {
-        std::thread& t;
-        ~Join() { if (t.joinable()) t.join(); }
-    } join_toucher{toucher};
-    HIPCHK(up(p.dmA, dmA, nA * m2 * sizeof(double2)));
-    if (dmB) HIPCHK(up(p.dmB, dmB, nB * m2 * sizeof(double2)));
-    if (dmT) HIPCHK(up(p.dmT, dmT, nT * m2 * sizeof(double2)));
-    if (dm_s) HIPCHK(up(p.dm_s, dm_s, m2 * sizeof(double2)));
-    HIPCHK(up(p.rho_init, rho_init, N2 * sizeof(double2)));
-    HIPCHK(up(p.opA, opA, N2 * sizeof(double2)));
-    HIPCHK(up(p.opB, opB, N2 * sizeof(double2)));
-    HIPCHK(up(p.opC, opC, N2 * sizeof(double2)));
-    HIPCHK(up(p.time, time, p.n_tfull * sizeof(double)));
-    HIPCHK(up(p.time_sparse, time_sparse, p.n_t * sizeof(double)));
+    const decltype(now()) t0 = now();
+    PageToucher toucher((void*)result, nres * sizeof(double2));
+    const size_t vb = N2 * sizeof(double2), mb = vb * N2;  // the inputs; pos (the blocked sweep's trunk ends) last
+    const struct { const void *dst, *src; size_t bytes; } ups[] = {
+        {p.dmA, in.dmA, in.nA * mb}, {p.dmB, in.dmB, in.nB * mb}, {p.dmT, in.dmT, in.nT * mb}, {p.dm_s, in.dm_s, mb},
+        {p.rho_init, in.rho_init, vb}, {p.opA, in.opA, vb}, {p.opB, in.opB, vb}, {p.opC, in.opC, vb},
+        {p.time, in.time, p.n_tfull * sizeof(double)}, {p.time_sparse, in.time_sparse, p.n_t * sizeof(double)},
+        {p.pos, blocked ? pos.data() : nullptr, p.n_t * sizeof(int)}};
+    for (const auto& u : ups)
+        if (u.src && u.bytes) HIPCHK(hipMemcpyAsync(const_cast<void*>(u.dst), u.src, u.bytes, hipMemcpyHostToDevice, s));
     if (blocked) {
-        // every result element is written by the blocked kernels (trunk column, partial-block outputs, dots)
-        HIPCHK(up(p.pos, pos.data(), p.n_t * sizeof(int)));
-        HIPCHK(launch_mapchain_blocked(p, pmax / p.L, s));
+        // every result element is written by the blocked kernels; n_chain from the last, largest trunk end (mode 0)
+        HIPCHK(launch_mapchain_blocked(p, p.mode == 0 ? pos.back() / p.L : 0, s));
     } else {
         HIPCHK(hipMemsetAsync(p.result, 0, nres * sizeof(double2), s));
-        HIPCHK(launch_mapchain(p, s));
+        HIPCHK(launch_mapchain(p, env.pipe, s));
     }
     const auto t1 = now();
-    toucher.join();
+    if (toucher.t.joinable()) toucher.t.join();
     const auto t2 = now();
-    if (tmg) HIPCHK(hipStreamSynchronize(s));
+    if (env.timing) HIPCHK(hipStreamSynchronize(s));
     const auto t3 = now();
     HIPCHK(hipMemcpyAsync(result, p.result, nres * sizeof(double2), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (tmg) {
-        const auto t4 = now();
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "pqd mapchain: upload+launch %.3f ms, page touch left %.3f ms, kernels left %.3f ms, download %.3f ms\n",
-                ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4));
-    }
+    if (env.timing) print_mc_timing({t0, t1, t2, t3, now()});
     return PQD_OK;
 }
 
@@ -2480,8 +2478,8 @@ int pqd_calc_onetime_parallel(pqd_ctx* ctx, const pqd_c128* dm_tl, const pqd_c12
     MapChainParams p{};
     p.mode = 0; p.dim = dim; p.n_t = n_t; p.n_tfull = n_tfull; p.n_tau = n_tau;
     // the tau loop reads maps up to index j_max - 1 + n_tau <= n_tfull - 1 (Fortran bounds)
-    return mapchain_run(ctx, p, dm_tl, (size_t)std::max(1, n_tfull - 1), nullptr, 0, nullptr, 0, nullptr, rho_init,
-                        opA, opB, opC, time, time_sparse, result);
+    return mapchain_run(ctx, p, {dm_tl, nullptr, nullptr, nullptr, rho_init, opA, opB, opC,
+                                 (size_t)std::max(1, n_tfull - 1), 0, 0, time, time_sparse}, result);
 }
 
 int pqd_calc_onetime_parallel_block(pqd_ctx* ctx, const pqd_c128* dm_block, const pqd_c128* dm_s,
@@ -2494,8 +2492,8 @@ int pqd_calc_onetime_parallel_block(pqd_ctx* ctx, const pqd_c128* dm_block, cons
     MapChainParams p{};
     p.mode = 1; p.dim = dim; p.n_t = n_t; p.n_tfull = n_tfull; p.n_tau = n_tb * nx_tau;
     p.n_map = n_map; p.n_tb = n_tb; p.nx_tau = nx_tau;
-    return mapchain_run(ctx, p, dm_block, n_map, nullptr, 0, nullptr, 0, dm_s, rho_init, opA, opB, opC, time,
-                        time_sparse, result);
+    return mapchain_run(ctx, p, {dm_block, nullptr, nullptr, dm_s, rho_init, opA, opB, opC, (size_t)n_map, 0, 0, time,
+                                 time_sparse}, result);
 }
 
 int pqd_calc_twotime_phonon_block(pqd_ctx* ctx, const pqd_c128* dm_taucs2, const pqd_c128* dm_sep1,
@@ -2511,14 +2509,14 @@ int pqd_calc_twotime_phonon_block(pqd_ctx* ctx, const pqd_c128* dm_taucs2, const
     MapChainParams p{};
     p.mode = 2; p.dim = dim; p.n_t = n_t; p.n_tfull = n_tfull; p.n_tau = n_tb * nx_tau;
     p.n_map = n_map; p.n_tb = n_tb; p.nx_tau = nx_tau; p.n_tauc = n_tauc;
-    return mapchain_run(ctx, p, dm_sep1, n_map, dm_sep2, n_map, n_tauc > 0 ? dm_taucs2 : nullptr,
-                        (size_t)n_tauc * n_map, dm_s, rho_init, opA, opB, opC, time, time_sparse, result);
+    return mapchain_run(ctx, p, {dm_sep1, dm_sep2, n_tauc > 0 ? dm_taucs2 : nullptr, dm_s, rho_init, opA, opB, opC,
+                                 (size_t)n_map, (size_t)n_map, (size_t)n_tauc * n_map, time, time_sparse}, result);
 }
 
 int pqd_propagate_tau(pqd_ctx* ctx, const pqd_c128* dm_tl, int32_t n_maps, const pqd_c128* rho_init,
                       int32_t n_tau, int32_t dim, int32_t j_start, pqd_c128* rho_out) {
     if (!ctx || !dm_tl || !rho_init || !rho_out) return fail(PQD_ERR_ARG, "NULL argument");
-    if (dim < 2 || dim > 6) return fail(PQD_ERR_UNSUPPORTED, "dim %d", dim);
+    if (!check_dim_2_6(dim)) return fail(PQD_ERR_UNSUPPORTED, "dim %d", dim);
     if (n_tau < 0 || j_start < 0 || j_start + n_tau > n_maps)
         return fail(PQD_ERR_ARG, "maps j_start+1..j_start+n_tau = %d..%d outside 1..%d", j_start + 1, j_start + n_tau, n_maps);
     HIPCHK(hipSetDevice(ctx->device));
@@ -2537,7 +2535,7 @@ int pqd_propagate_tau(pqd_ctx* ctx, const pqd_c128* dm_tl, int32_t n_maps, const
 int pqd_map_tail(pqd_ctx* ctx, const pqd_c128* M, int32_t N2, const pqd_c128* X, int32_t n_x, const pqd_c128* w,
                  int32_t n_steps, pqd_c128* out) {
     if (!ctx || !M || !X || !w || !out) return fail(PQD_ERR_ARG, "NULL argument");
-    if (!(N2 == 4 || N2 == 9 || N2 == 16 || N2 == 25 || N2 == 36)) return fail(PQD_ERR_UNSUPPORTED, "N2 %d", N2);
+    if (!n2_listed(N2)) return fail(PQD_ERR_UNSUPPORTED, "N2 %d", N2);
     if (n_x < 0 || n_steps < 0) return fail(PQD_ERR_ARG, "n_x %d n_steps %d", n_x, n_steps);
     if (n_x == 0 || n_steps == 0) return PQD_OK;
     HIPCHK(hipSetDevice(ctx->device));
@@ -2575,7 +2573,7 @@ static int four_time_common(pqd_ctx* ctx, FourTimeParams& p, const pqd_c128* dm_
                             int n_ops, pqd_c128* result, bool dyn, int row_lo = 0, int row_hi = INT_MAX) {
     if (!ctx || !dm_1 || !dm_2 || !rho_init || !t1 || !precalc || !result || (!dyn && !ops))
         return fail(PQD_ERR_ARG, "NULL argument");
-    if (p.dim < 2 || p.dim > 6) return fail(PQD_ERR_UNSUPPORTED, "dim %d", p.dim);
+    if (!check_dim_2_6(p.dim)) return fail(PQD_ERR_UNSUPPORTED, "dim %d", p.dim);
     if (p.n_t < 1 || p.n_map < 1 || p.n_precalc < 1 || !(p.dt > 0)) return fail(PQD_ERR_ARG, "bad sizes");
     {
         // every segment the call propagates over: fast_propagate (timebin_tl.f90:36-46) reads dm_tl_precalc(:, :, bit + 1)
@@ -2642,14 +2640,12 @@ static int four_time_common(pqd_ctx* ctx, FourTimeParams& p, const pqd_c128* dm_
     return PQD_OK;
 }
 
-int pqd_four_time_8op(pqd_ctx* ctx, const pqd_c128* dm_1, const pqd_c128* dm_2, const pqd_c128* rho_init,
-                      const double* t1, const pqd_c128* precalc, int32_t n_t, double dt, int32_t n_map,
-                      int32_t dim, const pqd_c128* ops8, int32_t early_only, int32_t late_t1_only, double tb,
-                      int32_t n_precalc, pqd_c128* result) {
+static FourTimeParams ft_params(int dim, int n_t, int n_map, int n_precalc, double dt, double tb, int variant = 0,
+                                int early_only = 0, int late_t1_only = 0) {
     FourTimeParams p{};
     p.dim = dim; p.n_t = n_t; p.n_map = n_map; p.n_precalc = n_precalc; p.dt = dt; p.tb = tb;
-    p.variant = 0; p.early_only = early_only; p.late_t1_only = late_t1_only;
-    return four_time_common(ctx, p, dm_1, dm_2, rho_init, t1, precalc, ops8, 8, result, false);
+    p.variant = variant; p.early_only = early_only; p.late_t1_only = late_t1_only;
+    return p;
 }
 
 int pqd_four_time_8op_rows(pqd_ctx* ctx, const pqd_c128* dm_1, const pqd_c128* dm_2, const pqd_c128* rho_init,
@@ -2657,25 +2653,29 @@ int pqd_four_time_8op_rows(pqd_ctx* ctx, const pqd_c128* dm_1, const pqd_c128* d
                            int32_t dim, const pqd_c128* ops8, int32_t early_only, int32_t late_t1_only, double tb,
                            int32_t n_precalc, int32_t row_lo, int32_t row_hi, pqd_c128* result) {
     if (row_lo < 0 || row_hi < row_lo || row_hi > n_t) return fail(PQD_ERR_ARG, "rows [%d, %d) outside [0, %d)", row_lo, row_hi, n_t);
-    FourTimeParams p{};
-    p.dim = dim; p.n_t = n_t; p.n_map = n_map; p.n_precalc = n_precalc; p.dt = dt; p.tb = tb;
-    p.variant = 0; p.early_only = early_only; p.late_t1_only = late_t1_only;
+    FourTimeParams p = ft_params(dim, n_t, n_map, n_precalc, dt, tb, 0, early_only, late_t1_only);
     return four_time_common(ctx, p, dm_1, dm_2, rho_init, t1, precalc, ops8, 8, result, false, row_lo, row_hi);
+}
+
+int pqd_four_time_8op(pqd_ctx* ctx, const pqd_c128* dm_1, const pqd_c128* dm_2, const pqd_c128* rho_init,
+                      const double* t1, const pqd_c128* precalc, int32_t n_t, double dt, int32_t n_map,
+                      int32_t dim, const pqd_c128* ops8, int32_t early_only, int32_t late_t1_only, double tb,
+                      int32_t n_precalc, pqd_c128* result) {
+    FourTimeParams p = ft_params(dim, n_t, n_map, n_precalc, dt, tb, 0, early_only, late_t1_only);
+    return four_time_common(ctx, p, dm_1, dm_2, rho_init, t1, precalc, ops8, 8, result, false, 0, n_t);
 }
 
 int pqd_four_time(pqd_ctx* ctx, const pqd_c128* dm_1, const pqd_c128* dm_2, const pqd_c128* rho_init,
                   const double* t1, const pqd_c128* precalc, int32_t n_t, double dt, int32_t n_map, int32_t dim,
                   const pqd_c128* ops4, double tb, int32_t n_precalc, pqd_c128* result) {
-    FourTimeParams p{};
-    p.dim = dim; p.n_t = n_t; p.n_map = n_map; p.n_precalc = n_precalc; p.dt = dt; p.tb = tb; p.variant = 1;
+    FourTimeParams p = ft_params(dim, n_t, n_map, n_precalc, dt, tb, 1);
     return four_time_common(ctx, p, dm_1, dm_2, rho_init, t1, precalc, ops4, 4, result, false);
 }
 
 int pqd_dynamics_t1(pqd_ctx* ctx, const pqd_c128* dm_1, const pqd_c128* dm_2, const pqd_c128* rho_init,
                     const double* t1, const pqd_c128* precalc, int32_t n_t, double dt, int32_t n_map,
                     int32_t dim, double tb, int32_t n_precalc, pqd_c128* result) {
-    FourTimeParams p{};
-    p.dim = dim; p.n_t = n_t; p.n_map = n_map; p.n_precalc = n_precalc; p.dt = dt; p.tb = tb;
+    FourTimeParams p = ft_params(dim, n_t, n_map, n_precalc, dt, tb);
     return four_time_common(ctx, p, dm_1, dm_2, rho_init, t1, precalc, nullptr, 0, result, true);
 }
 

@@ -1,6 +1,7 @@
-"""Bit-for-bit comparison of the PT propagation paths between two libpqd builds.
+"""Bit-for-bit comparison of the PT propagation paths and of the map-chain family between two libpqd builds.
 
 usage: python scripts/compare_split_builds.py LIB_A LIB_B [--only SUBSTRING[,SUBSTRING...]] [--log FILE]
+                                              [--names NAME_A,NAME_B  (what the log calls the two; default: the paths)]
 
 For every case one child process per library (one after the other, each under its own time limit, the library chosen
 through PQD_LIB, the case's switches in its environment) runs a plan on seeded inputs and saves every trajectory's
@@ -10,8 +11,16 @@ tests/test_gpu_msplit.py: three systems, ragged windows, MTOs before and after a
 last step among them), 150 steps, and a schedule that changes the slice at most steps and repeats it at some, so the
 split kernels' schedule reader crosses its 64-entry chunk boundary twice. The cases together run every instance of
 pt_split_kernel and pt_msplit_kernel (named in the case id), their switches, and one case per N2 of the batched sweep,
-the quad kernel and the free propagators (the launch layer's dispatch). Exit status 0: all equal; 1: a difference;
-2: a child failed (the run stops there: nothing more is started on the device)."""
+the quad kernel and the free propagators (the launch layer's dispatch).
+
+The map-chain family (mapchain.hip; case ids mc_* and ft_*, e.g. --only mc_,ft_): the three sweep modes at dims 2-6 on
+the default path, with PQD_MC_BLOCKED=0, with PQD_MC_BLOCKED=0 PQD_MC_PIPE=0 and (modes 0, 1) with PQD_MC_L=8;
+propagate_tau and map_tail at dims 2-6; four_time_8op with its three flag settings, four_time and dynamics_t1 at dims
+2, 3, 5. Inputs are seeded and built like those of tests/test_gpu_mapchain_paths.py and helpers.timebin_inputs: the
+last wave of every sweep is part-filled, trunk ends lie on both sides of n_tb, and t1 segments reach the precalc maps.
+
+Exit status 0: all equal; 1: a difference; 2: a child failed (the run stops there: nothing more is started on the
+device)."""
 import argparse
 import os
 import subprocess
@@ -25,7 +34,8 @@ sys.path.insert(0, HERE)
 
 N_STEPS = 150
 SWITCHES = ("PQD_SPLIT", "PQD_SPLIT_GRAN", "PQD_SPLIT_OW", "PQD_SPLIT_XCD", "PQD_SPLIT_L2", "PQD_SPLIT_SPIN",
-            "PQD_MSPLIT", "PQD_MS_L2", "PQD_MS_PTM", "PQD_MS_TB", "PQD_ABLATE", "PQD_FPM", "PQD_QUAD")
+            "PQD_MSPLIT", "PQD_MS_L2", "PQD_MS_PTM", "PQD_MS_TB", "PQD_ABLATE", "PQD_FPM", "PQD_QUAD",
+            "PQD_MC_BLOCKED", "PQD_MC_PIPE", "PQD_MC_L", "PQD_MC_TIMING")
 SPLIT, MSPLIT = "split groups", "split groups, several trajectories per group"
 BATCHED, QUAD = "batched lock-step sweep", "register-resident TLS quads"
 
@@ -68,6 +78,21 @@ def _cases():
         c[f"free_N2={N * N}_fpm=0"] = ("free", dict(N=N), dict(PQD_FPM=0), None)
     for chi in (16, 32, 64):
         c[f"quad_N2=4_chi={chi}"] = ("pt", dict(N=2, chi=chi, n_traj=9), dict(PQD_SPLIT=0, PQD_QUAD=2), QUAD)
+    # the map-chain family
+    mc_env = {"default": {}, "noblocked": dict(PQD_MC_BLOCKED=0), "noblocked_nopipe": dict(PQD_MC_BLOCKED=0, PQD_MC_PIPE=0),
+              "L=8": dict(PQD_MC_L=8)}
+    for N in (2, 3, 4, 5, 6):
+        for mode in (0, 1, 2):
+            for tag, env in mc_env.items():
+                if not (mode == 2 and tag == "L=8"):
+                    c[f"mc_mode{mode}_dim={N}_{tag}"] = ("sweep", dict(N=N, mode=mode), env, None)
+        c[f"mc_propagate_tau_dim={N}"] = ("propagate_tau", dict(N=N), {}, None)
+        c[f"mc_map_tail_dim={N}"] = ("map_tail", dict(N=N), {}, None)
+    for N in (2, 3, 5):
+        for tag, flags in (("plain", (False, False)), ("early", (True, False)), ("late_t1", (False, True))):
+            c[f"ft_8op_{tag}_dim={N}"] = ("ft8", dict(N=N, flags=flags), {}, None)
+        c[f"ft_4op_dim={N}"] = ("ft4", dict(N=N), {}, None)
+        c[f"ft_dynamics_t1_dim={N}"] = ("dyn", dict(N=N), {}, None)
     return c
 
 
@@ -111,8 +136,61 @@ def _schedule(n_slices, seed):
     return s
 
 
+def _mapchain_child(kind, p):
+    """the outputs of one map-chain case; maps, operators and states as in tests/test_gpu_mapchain_paths.py"""
+    from pyaceqd_amd.timebin import timebin_tl as TB
+    from pyaceqd_amd.two_time import propagate_tau_module as M
+    from tests import helpers as H
+    dim = p["N"]
+    N2 = dim * dim
+    rng = np.random.default_rng(900 + 10 * dim + p.get("mode", 0))
+    mk = lambda: np.eye(N2) + 0.05 * (rng.normal(size=(N2, N2)) + 1j * rng.normal(size=(N2, N2))) / dim  # noqa: E731
+    F = lambda maps: np.asfortranarray(np.asarray(maps).transpose(1, 2, 0))  # noqa: E731
+    if kind in ("ft8", "ft4", "dyn"):
+        z = H.timebin_inputs(dim)
+        a = (z["dm_1"], z["dm_2"], z["rho"], z["t1"], z["precalc"], z["dt"], z["dim"])
+        if kind == "ft8":
+            return {"G": TB.four_time_8op(*a, *z["ops8"], *p["flags"], z["tb"])}
+        if kind == "ft4":
+            return {"G": TB.four_time(*a, *z["ops8"][:4], z["tb"])}
+        return {"rho": TB.dynamics_t1(*a, z["tb"])}
+    rho = H.random_rho(dim).reshape(N2)
+    if kind == "propagate_tau":
+        maps = F([mk() for _ in range(30)])
+        return {f"n_tau={n}_j_start={j}": M.propagate_tau(maps, rho, n, dim, j) for n, j in ((0, 0), (25, 0), (5, 25))}
+    if kind == "map_tail":
+        X = rng.normal(size=(N2, 37)) + 1j * rng.normal(size=(N2, 37))  # 37 rows: the last wave is part-filled
+        w = rng.normal(size=N2) + 1j * rng.normal(size=N2)
+        return {"out": M.map_tail(mk(), X, w, 300)}
+    n_t = max(2 * (64 // N2) + 1, 7)  # odd: full waves and a part-filled last one (dim 6: one trajectory a wave)
+    ops = [rng.normal(size=(dim, dim)) + 1j * rng.normal(size=(dim, dim)) for _ in range(3)]
+    if p["mode"] == 0:
+        n_tau, n_tfull = 40, 260
+        maps = F([mk() for _ in range(n_tfull - 1)])
+        time = np.round(np.arange(n_tfull) * 0.1, 6)
+        ts = np.sort(np.concatenate([[0.0, 0.05, 0.8], np.round(rng.uniform(0.0, 10.85, n_t - 3), 2)]))
+        return {"G": M.calc_onetime_parallel(maps, rho, n_tau, dim, *ops, time, ts)}
+    time = np.round(np.arange(60) * 0.1, 6)
+    if p["mode"] == 1:
+        n_tb, nx_tau, n_map = 12, 9, 7
+        # trunk ends j = 1 + #{time < ts}: 1, inside n_tb, n_tb, n_tb + 1 and past it
+        ts = np.sort(np.concatenate([[0.0, 0.4, 1.1, 1.2, 3.3], np.round(rng.uniform(0.0, 2.4, n_t - 5), 2)]))
+        return {"G": M.calc_onetime_parallel_block(F([mk() for _ in range(n_map)]), np.asfortranarray(mk()), rho, n_tb,
+                                                   nx_tau, dim, *ops, time, ts)}
+    n_tb, nx_tau, n_map, n_tauc = 5, 3, 7, n_t // 2
+    sep1, sep2, dm_s = F([mk() for _ in range(n_map)]), F([mk() for _ in range(n_map)]), np.asfortranarray(mk())
+    tc = np.zeros((N2, N2, n_tauc, n_map), dtype=complex, order="F")
+    for i in range(n_tauc):
+        for jj in range(n_map):
+            tc[:, :, i, jj] = mk()
+    ts = np.sort(np.concatenate([[0.0, 0.15, 0.4, 0.5, 0.85], np.round(rng.uniform(0.0, 1.2, n_t - 5), 2)]))
+    return {"G": M.calc_twotime_phonon_block(tc, sep1, sep2, dm_s, rho, n_tb, nx_tau, dim, *ops, time, ts)}
+
+
 def _child(case, out):
     kind, p, _, want = _cases()[case]
+    if kind not in ("pt", "free"):
+        return np.savez(out, **_mapchain_child(kind, p))
     from pyaceqd_amd import engine, pt as ptmod
     from pyaceqd_amd.engine import Grid
     from tests import helpers as H
@@ -150,6 +228,7 @@ def main():
     ap.add_argument("libs", nargs="*")
     ap.add_argument("--only", default="")
     ap.add_argument("--log", default="")
+    ap.add_argument("--names", default="")
     ap.add_argument("--child", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -166,7 +245,8 @@ def main():
             log.write(line + "\n")
             log.flush()
 
-    say(f"# A = {a.libs[0]}  B = {a.libs[1]}; one child process per case and library; np.array_equal on every output, "
+    names = a.names.split(",") if a.names else a.libs
+    say(f"# A = {names[0]}  B = {names[1]}; one child process per case and library; np.array_equal on every output, "
         "the plan's path, fallbacks and description as text")
     n_diff = 0
     cases = {k: v for k, v in _cases().items() if any(t in k for t in a.only.split(","))}
@@ -194,7 +274,8 @@ def main():
             bad = [k for k in sorted(set(A) | set(B))
                    if k not in A or k not in B or A[k].shape != B[k].shape or not np.array_equal(A[k], B[k])]
             n_diff += bool(bad)
-            what = str(A["info"]) if "info" in A else f"M{tuple(A['M'].shape)}"
+            what = (str(A["info"]) if "info" in A else f"M{tuple(A['M'].shape)}" if "M" in A
+                    else ", ".join(f"{k}{tuple(v.shape)}" for k, v in sorted(A.items())))
             say(f"{'DIFFER ' + ','.join(bad) if bad else 'equal '} {cid}  [{len(A)} arrays; {what}]")
     say(f"# {len(cases)} cases, {n_diff} differ")
     return 1 if n_diff else 0

@@ -7,6 +7,8 @@
 * mode 2 (calc_twotime_phonon_block) at the dims with padding lanes (3 and 5) and at dim 2 over three waves, with
   n_tauc = 0, 1, a middle value and n_t, n_map below and above n_tb, and trunk ends at 1, inside n_tb, at n_tb and at
   n_tb + 1 (from n_tb on the wrap test `jj + j_start == n_tb + 1` never fires) and further out.
+* tau windows shorter than the pipelined kernels' prefetch depth (dims 2 and 3, all three modes): only the guarded
+  remainder loop runs and the lookahead map cursor is past the last step from its first load on.
 * propagate_tau with n_tau = 0 and j_start = 0, and at the end of the map stack.
 * the refusal of a mode-0 sweep that would read past dm_tl, with PQD_MC_BLOCKED=0.
 
@@ -146,6 +148,67 @@ def test_twotime_phonon_block_accepts_no_taucs_array():
     ref = M.calc_twotime_phonon_block(*a)
     a[0] = np.zeros((9, 9, 0, 0), dtype=complex, order="F")
     assert np.array_equal(M.calc_twotime_phonon_block(*a, n_map=7), ref)
+
+
+def _short_window_cases(mode):
+    if mode == 0:
+        return [(n_tau,) for n_tau in (0, 1, 2, 3, 5)]
+    return [(n_tb, nx_tau, n_map) for n_tb, nx_tau in ((2, 0), (1, 1), (1, 2), (3, 1), (1, 3), (5, 1)) for n_map in (1, 3, 7)]
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("dim", [2, 3])
+def test_windows_shorter_than_the_prefetch_depth(monkeypatch, dim, mode):
+    """tau windows of 0 to 5 steps at dims 2 and 3, where the pipelined kernels prefetch 4 and 2 maps ahead: the
+    unrolled loop runs once at most, the guarded remainder does the work, and the lookahead map cursor runs past the
+    last step from its first load on (it must hand out a valid map there). dim 3 has padding lanes; n_t leaves one
+    trajectory in the third wave. Every shape on the default path, with PQD_MC_BLOCKED=0 (modes 0 and 1: mode 2 has no
+    blocked sweep, its default path is that one already and is not run twice) and with PQD_MC_PIPE=0 in addition, each
+    against the oracle."""
+    N2 = dim * dim
+    n_t = 2 * (64 // N2) + 1
+    rng = np.random.default_rng(700 + 10 * dim + mode)
+    time = 0.1 * np.arange(30)
+    ts = np.sort(np.concatenate([[0.0], rng.uniform(0.0, 1.2, n_t - 1)]))
+    ops = _ops(rng, dim)
+    rho = H.random_rho(dim, seed=700 + dim).reshape(N2)
+    maps = [_mk(rng, N2, dim) for _ in range(29)]  # dm_tl; its head serves as dm_block / dm_sep1
+    sep2 = [_mk(rng, N2, dim) for _ in range(7)]
+    dm_s = np.asfortranarray(_mk(rng, N2, dim))
+    n_tauc = n_t // 2
+    tc = np.zeros((N2, N2, n_tauc, 7), dtype=complex, order="F")
+    for i in range(n_tauc):
+        for jj in range(7):
+            tc[:, :, i, jj] = _mk(rng, N2, dim)
+    paths = [{}, {"PQD_MC_BLOCKED": "0"}, {"PQD_MC_BLOCKED": "0", "PQD_MC_PIPE": "0"}]
+    worst = 0.0
+    for case in _short_window_cases(mode):
+        if mode == 0:
+            a, n_tau = (F(maps), rho, case[0], dim, *ops, time, ts), case[0]
+            name = "calc_onetime_parallel"
+        else:
+            n_tb, nx_tau, n_map = case
+            n_tau = n_tb * nx_tau
+            if mode == 1:
+                a = (F(maps[:n_map]), dm_s, rho, n_tb, nx_tau, dim, *ops, time, ts)
+                name = "calc_onetime_parallel_block"
+            else:
+                a = (np.asfortranarray(tc[:, :, :, :n_map]), F(maps[:n_map]), F(sep2[:n_map]), dm_s, rho, n_tb, nx_tau,
+                     dim, *ops, time, ts)
+                name = "calc_twotime_phonon_block"
+        ref = getattr(oracle, name)(*a)
+        assert ref.shape == (n_t, n_tau + 1) and np.all(np.isfinite(ref))
+        for env in (paths[::2] if mode == 2 else paths):
+            for k in ("PQD_MC_BLOCKED", "PQD_MC_PIPE"):
+                monkeypatch.delenv(k, raising=False)
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            got = getattr(M, name)(*a)
+            assert got.shape == ref.shape
+            e = rel(got, ref)
+            worst = max(worst, e)
+            assert e < 1e-11, (case, env, e)
+    print(f"short windows dim {dim} mode {mode}: worst GPU vs oracle {worst:.3e}")
 
 
 @pytest.mark.parametrize("dim", DIMS)
