@@ -298,6 +298,18 @@ int pqd_plan_sweep_stage(const pqd_plan* plan, int32_t* n_blocks);
  * and the multi-trajectory group tables (0 where the plan has none). The decisions set speed, not results; tests pin
  * them with this line. PQD_ERR_ARG if the line and its terminating NUL do not fit len bytes */
 int pqd_plan_describe(const pqd_plan* plan, char* buf, int32_t len);
+/* Liouville rows that can ever be nonzero: live[a] = 1 for the rows alpha = i N + j reachable from the
+ * nonzero entries of rho0 through L0 of every system, S_p and T_p of every channel with a nonzero sample anywhere in its
+ * array, and the superoperators of the trajectories' MTOs (traj may be NULL: none), each entry judged by exact != 0 as
+ * it is uploaded; 0 for the rows that are exactly zero at every step of every trajectory. live: N*N bytes. Host only: no
+ * context, no device. The batched sweep gives rows with 0 no PT unit (PQD_LIVE_ROWS=0: all rows; 2: synchronize also
+ * checks that no stored free propagator leads from a live column into such a row, PQD_ERR_NUMERIC otherwise).
+ * pqd_plan_live_rows: the mask the plan's sweep uses (len = N*N): all 1 where it leaves nothing out (another path, no
+ * PT, a wide PT, PQD_LIVE_ROWS=0). pqd_plan_describe ends with " live=<hex mask> parts=<0|1>" for a plan that leaves
+ * rows out (parts: the lean instance deals the live rows in quarters, PQD_LIVE_PART=0: whole rows), and is the line it
+ * always was for every other plan. */
+int pqd_live_rows(int32_t n_sys, const pqd_system* systems, const pqd_c128* rho0, const pqd_traj* traj, uint8_t* live);
+int pqd_plan_live_rows(const pqd_plan* plan, uint8_t* live, int32_t len);
 /* average kernel durations (ms) of the executions since the last reset (the most recent 64 at most),
  * from HIP events on the launch stream: [0] free-propagator kernel, [1] sweep kernel; n = executions */
 int pqd_plan_timing(pqd_plan* plan, double* ms_free, double* ms_sweep, int32_t* n, int32_t reset);

@@ -217,6 +217,11 @@ struct SweepParams {
                              //   and W(n + 1) (and the closure vector step n + 1 reads) the fast region stages in LDS during
                              //   the PT phase of step n (pt_sweep.hip LeanStage); -1: the block's slots mix systems and
                              //   load these operands in place. NULL: no block stages (PQD_LEAN_STAGE=0, or blk_fast NULL)
+    int lean_parts;          // 1 (lean plans with rows that stay zero, pqd_host.cpp lean_part_units): a wave's first unit may
+                             //   be a partial one, (slice, row, -1, g0 | ng << 4): column groups g0 .. g0 + ng - 1 (ng 1 or
+                             //   2, g0 a multiple of ng, 16 columns each) of the row, followed by one whole one-row unit.
+                             //   The PT phase then has a barrier between the partial units' reads of their rows and the
+                             //   writes of their columns (pt_sweep.hip LeanPt::run_parts). No other instance sees such a list
 };
 
 // split groups with several trajectories per group (pt_msplit.hip)
@@ -431,6 +436,9 @@ hipError_t launch_free_win(const FreePropParams& p, hipStream_t s);
 // flags |= 1 if any of the n complex values is NaN or Inf (one pass over the output buffer at synchronize: the sweep
 // kernels carry no per-store check, which cost 1.7% of the headline kernel)
 hipError_t launch_check_finite(const double2* v, int64_t n, unsigned* flags, hipStream_t s);
+// n_ops row-major N2 x N2 operators (N2 <= 64): flags bit 1 where an entry [row not in live][column in live] is not 0
+hipError_t launch_check_dead_block(const double2* v, int64_t n_ops, int N2, unsigned long long live, unsigned* flags,
+                                   hipStream_t s);
 hipError_t launch_table(const double2* out, const long long* woff, const int* wbeg, const int* wend,
                         const long long* toff, int n_traj, int n_out, double t_start, double dt, double2* table,
                         hipStream_t s);

@@ -270,6 +270,10 @@ struct pqd_plan {
     DevBuf<int> blk_stage;        // per block: the one system whose column operands the fast region stages, or -1
     int n_stage = 0;              // blocks of a lean plan that stage (pqd_plan_sweep_stage)
     std::vector<int> h_unit0;     // per wave: the slice of its first PT row unit (< 0: the wave has none)
+    // Liouville rows the main batched sweep contracts with the PT (live_row_mask; all 1 where the plan skips none:
+    // PQD_LIVE_ROWS=0, another path, no PT) and whether synchronize verifies the operators' zero blocks (PQD_LIVE_ROWS=2)
+    std::vector<uint8_t> live;
+    bool live_check = false;
     int64_t traj_steps = 0;       // executed trajectory-steps per execute (shared trunks counted once)
     int branch = 1;               // shared-trunk activation in the batched sweep (PQD_BRANCH)
     // trunk pre-pass (pqd_host.cpp plan_trunks): one MTO-free trajectory per system writes the checkpoints the
@@ -499,7 +503,7 @@ void pqd_pt_destroy(pqd_pt* pt) { delete pt; }
 // each has one field.
 struct PlanEnv {
     int split, msplit, ms_tb, ms_ptm, fp4, fpm, pt_mode, cmul3, trpre, bt, colbig, trunk, quad, qpw, qcg, qprio, win,
-        rowpair, ablate, hbpt_g;
+        rowpair, ablate, hbpt_g, live_rows, live_part;
     bool ms_l2, split_ow, split_gran, split_xcd, sweep_lean, lean_ro, lean_stage, pt_mode_set, fuse, branch, idle, unitbal, split_l2, hilbert;
     unsigned split_spin;
 };
@@ -537,6 +541,8 @@ static PlanEnv read_plan_env() {
     v.idle = num("PQD_IDLE", 1) != 0;           // idle half steps copy one operator (0: compute every half step)
     v.win = num("PQD_WIN", 1);                  // pulse windows: 0 never, 1 when they leave out a tenth, 2 always
     v.unitbal = num("PQD_UNITBAL", 1) != 0;     // PT row units split to balance the waves (0: whole units)
+    v.live_rows = num("PQD_LIVE_ROWS", 1);      // PT rows that stay exactly zero get no unit (0: all rows; 2: and verify M, F)
+    v.live_part = num("PQD_LIVE_PART", 1) != 0;  // ... and the lean instance deals the live rows in quarters (0: whole rows)
     v.rowpair = set("PQD_ROWPAIR") ? num("PQD_ROWPAIR", 1) != 0 : -1;  // 0: one PT row per unit; -1 unset
     v.ablate = num("PQD_ABLATE", 0);            // kernel phase ablation and stamps (raw value; measurements only)
     const char* spin = getenv("PQD_SPLIT_SPIN");
@@ -700,11 +706,19 @@ int pqd_dressed_timing(pqd_ctx* ctx, double* ms_kernel) {
 // PTs, e.g. 16 biexciton rows over 9 slices) are contracted together in units of up to rmax rows, so one L2
 // read of a slice feeds all of them. Units (cost = rows) go to the least-loaded wave, largest first. A unit is
 // (slice, row 0, row 1 or -1, row 2 | row 3 << 16 or -1, a missing row 3 being 0x7FFF); each wave's list ends
-// with slice -1.
-static std::vector<int4> pt_row_units(const std::vector<int>& gmap, int NW, int rmax, bool balance) {
+// with slice -1. live: rows with 0 stay exactly zero (live_row_mask) and get no unit: the kernels leave them
+// untouched, whole row blocks and dormant slots included (NULL: every row; with every row live the list is the same).
+// row_cap > 0: at most that many rows per wave, the others returned in `left` (lean_part_units deals them in parts)
+static std::vector<int4> pt_row_units(const std::vector<int>& gmap, int NW, int rmax, bool balance,
+                                      const std::vector<uint8_t>* live = nullptr, int row_cap = 0,
+                                      std::vector<int>* left = nullptr) {
     const int N2 = (int)gmap.size();
     std::vector<int4> units;
     std::vector<int> done(N2, 0);
+    int n_live = N2;
+    if (live)
+        for (int a = 0; a < N2; ++a)
+            if (!(*live)[a]) { done[a] = 1; --n_live; }
     for (int a = 0; a < N2; ++a) {
         if (done[a]) continue;
         int rows[4] = {-1, -1, -1, -1}, cnt = 0;
@@ -723,8 +737,9 @@ static std::vector<int4> pt_row_units(const std::vector<int>& gmap, int NW, int 
     // once more from L2 per extra wave). Six-level dictionary PT (9 slices x 4 rows, 8 waves): max 5 rows per wave
     // instead of 8 (one wave held two 4-row units). Least-loaded first, so the two waves of a SIMD (w, w + NW / 2)
     // also stay balanced: their MFMAs share its matrix pipe
-    int T = (N2 + NW - 1) / NW;
+    int T = (n_live + NW - 1) / NW;
     if (!balance) T = 1 << 20;  // PQD_UNITBAL=0 (A/B): whole units, least loaded
+    if (row_cap > 0) T = row_cap;
     std::vector<int> pending;  // rows of split units, slice-ordered
     for (const int4& e : units) {
         int w = -1;
@@ -743,6 +758,10 @@ static std::vector<int4> pt_row_units(const std::vector<int>& gmap, int NW, int 
         int w = 0;  // the least-loaded wave takes as many rows of this slice as fit (at most rmax)
         for (int k = 1; k < NW; ++k)
             if (load[k] < load[w]) w = k;
+        if (row_cap > 0 && load[w] >= row_cap) {  // every wave is full: the rest goes back to the caller
+            left->assign(pending.begin() + i, pending.end());
+            break;
+        }
         const int room = std::max(1, std::min(rmax, T - load[w]));
         int rows[4] = {-1, -1, -1, -1}, cnt = 0;
         const int g = gmap[pending[i]];
@@ -756,6 +775,39 @@ static std::vector<int4> pt_row_units(const std::vector<int>& gmap, int NW, int 
     std::vector<int4> out((size_t)NW * umax, make_int4(-1, 0, -1, -1));
     for (int w = 0; w < NW; ++w)
         for (size_t k = 0; k < per[w].size(); ++k) out[(size_t)w * umax + k] = per[w][k];
+    return out;
+}
+
+// The lean instance's list for a plan some of whose rows stay zero (pt_sweep.hip LeanPt::run_parts). Whole rows balance
+// the waves only in steps of a row: 10 live rows over 8 waves leave two SIMDs with three rows and two with two, and the
+// PT phase lasts as long as the fullest. So the rows are dealt in quarters (one of a slice's NG = 4 column groups of 16
+// columns): every wave aims at Tq = ceil(4 live / NW) quarters, takes one whole row first, and the rows left over are cut
+// into partial units of ng = 1 or 2 column groups, one per wave, in wave order (waves 0 .. NW/2 - 1 are one per SIMD, so
+// the two waves of a SIMD, w and w + NW/2, stay level). 10 rows: a whole row and a quarter on every wave, 1.25 rows on
+// the critical path instead of 2. A wave's list is [partial,] whole, end: the partial unit first, because its columns
+// are written behind a barrier the whole unit then hides. Empty where whole rows do as well (live <= NW or two whole
+// rows per wave) or where the rest does not fit one partial unit of at most two groups per wave (live 13, 14): the
+// caller keeps the whole-row list of the live rows.
+static std::vector<int4> lean_part_units(const std::vector<int>& gmap, int NW, const std::vector<uint8_t>& live) {
+    constexpr int NG = 4;
+    int n_live = 0;
+    for (uint8_t v : live) n_live += v != 0;
+    const int Tq = (NG * n_live + NW - 1) / NW;
+    if (n_live <= NW || Tq / NG != 1) return {};
+    std::vector<int> left;
+    const std::vector<int4> whole = pt_row_units(gmap, NW, 1, true, &live, 1, &left);
+    const size_t wmax = whole.size() / NW;
+    for (int w = 0; w < NW; ++w)
+        if (whole[w * wmax].x < 0 || whole[w * wmax].z >= 0 || (wmax > 1 && whole[w * wmax + 1].x >= 0)) return {};
+    const int quarters = NG * (int)left.size(), ng = quarters > NW ? 2 : 1;
+    if (left.empty() || quarters > NW * ng || ng > Tq - NG) return {};
+    std::vector<int4> out((size_t)NW * 3, make_int4(-1, 0, -1, -1));
+    for (int w = 0; w < NW; ++w) {
+        const int q = w * ng;  // this wave's first quarter of the rows left
+        size_t k = (size_t)w * 3;
+        if (q < quarters) out[k++] = make_int4(gmap[left[q / NG]], left[q / NG], -1, (q % NG) | (ng << 4));
+        out[k] = whole[w * wmax];
+    }
     return out;
 }
 
@@ -902,6 +954,7 @@ static void finalize_trunks(pqd_plan* P) {
     k.ev_start = P->tk_evstart.p; k.out = P->tk_out.p;
     k.ck_map = P->tk_ckmap.p; k.ck_stride = P->n_steps + 1;
     k.lean = 0;
+    k.lean_parts = 0;
     k.blk_fast = nullptr;
     k.blk_stage = nullptr;
     const int nw = P->tk_BT * sweep_wpt(P->N2, P->tk_BT, P->CHI);
@@ -1053,6 +1106,49 @@ static MtoEvents compose_mtos(int N, const pqd_traj* tr) {
     if (evs.empty()) evs.push_back(make_int4(-1, -1, 0, 0));
     if (sops.empty()) sops.assign(m2, 0.0);
     return E;
+}
+
+// Liouville rows that can ever be nonzero in a plan (pqd_live_rows): the closure of the initial state's
+// nonzero entries under the edges b -> a of every operator the sweep applies to the system index: L0 of every system,
+// S_p and T_p of every channel with a nonzero sample anywhere in its sample array, and every MTO superoperator, each
+// judged by exact != 0 on the values as they are uploaded. No edge leads from a live row into a dead one, so the
+// [dead row, live column] block of the generator is zero at every time, and with it that block of every sum and
+// product of such matrices: the Taylor / squaring exponentials, F = M_a M_b and the idle operators (with 3M products
+// too: each of the three real products has an exact-zero factor). The PT contraction is diagonal in the row index.
+// A dead row therefore holds exact zeros at every step of every trajectory, and its PT contraction is skipped.
+static std::vector<uint8_t> live_row_mask(int n_sys, const pqd_system* systems, const cd* rho0, const MtoEvents& E) {
+    const int N = systems[0].dim, N2 = N * N;
+    const size_t m2 = (size_t)N2 * N2;
+    std::vector<uint8_t> edge(m2, 0);
+    auto add = [&](const cd* Mx) {
+        for (size_t k = 0; k < m2; ++k)
+            if (Mx[k] != cd(0.0)) edge[k] = 1;
+    };
+    for (int k = 0; k < n_sys; ++k) {
+        Generators G;
+        build_generators(&systems[k], G);
+        add(G.L0.data());
+        for (int p = 0; p < systems[k].n_chan; ++p) {
+            bool driven = false;
+            for (int q = 0; q < systems[k].n_samples && !driven; ++q)
+                driven = G.samples[(size_t)p * systems[k].n_samples + q] != cd(0.0);
+            if (!driven) continue;
+            add(G.S.data() + p * m2);
+            add(G.T.data() + p * m2);
+        }
+    }
+    for (size_t k = 0; k + m2 <= E.sops.size(); k += m2) add(E.sops.data() + k);
+    std::vector<uint8_t> live(N2, 0);
+    std::vector<int> todo;
+    for (int a = 0; a < N2; ++a)
+        if (rho0[a] != cd(0.0)) { live[a] = 1; todo.push_back(a); }
+    while (!todo.empty()) {
+        const int b = todo.back();
+        todo.pop_back();
+        for (int a = 0; a < N2; ++a)
+            if (edge[(size_t)a * N2 + b] && !live[a]) { live[a] = 1; todo.push_back(a); }
+    }
+    return live;
 }
 
 // the plan's inputs on the device: generators for the free propagators (one table entry per system), MTO events,
@@ -1500,7 +1596,26 @@ static int fill_sweep_params(pqd_plan* P, const pqd_pt* pt, const PlanEnv& env, 
         const int nw = P->BT * sweep_wpt(P->N2, P->BT, P->CHI);
         int rmax = sweep_rmax(P->N2, P->BT, P->CHI);
         if (env.rowpair >= 0) rmax = std::max(1, std::min(rmax, env.rowpair ? rmax : 1));
-        std::vector<int4> u = pt_row_units(pt->gmap_h, nw, rmax, env.unitbal);
+        // rows that stay exactly zero get no unit (P->live: all 1 unless the main path is this sweep and PQD_LIVE_ROWS
+        // is on). The lean instance balances what is left below row granularity (lean_part_units; PQD_LIVE_PART=0: whole
+        // rows only); whether the plan will run it is asked with the fields fill_sweep_params sets further down
+        bool dead = false;
+        for (uint8_t v : P->live) dead = dead || !v;
+        std::vector<int4> u = pt_row_units(pt->gmap_h, nw, rmax, env.unitbal, dead ? &P->live : nullptr);
+        if (dead && env.live_part && env.unitbal && env.rowpair < 0) {
+            SweepParams t = sp;
+            t.fuse = (!P->nopt && ns > 0 && env.fuse) ? 1 : 0;
+            t.trpre = t.fuse ? env.trpre : 0;
+            t.units = u.data();  // (only asked whether a list exists)
+            t.umax = 3;
+            if (sweep_lean_ok(P, t, env)) {
+                std::vector<int4> pu = lean_part_units(pt->gmap_h, nw, P->live);
+                if (!pu.empty()) {
+                    u.swap(pu);
+                    sp.lean_parts = 1;
+                }
+            }
+        }
         HIPCHK(P->units.upload(u.data(), u.size(), s));
         P->h_units = fnv1a(u);
         sp.units = P->units.p;
@@ -1532,6 +1647,8 @@ static int fill_sweep_params(pqd_plan* P, const pqd_pt* pt, const PlanEnv& env, 
     // a static bias between the grid halves gains nothing; profiles/r03/quad_prio.log)
     sp.qprio = env.qprio;
     sp.lean = sweep_lean_ok(P, sp, env) ? 1 : 0;
+    if (sp.lean_parts && !sp.lean)  // partial units are read by the lean instance alone (asked above with these fields)
+        return fail(PQD_ERR_UNSUPPORTED, "internal: a unit list with partial units outside the lean instance");
     // the lean instance's readout inside the fused column phase (PQD_LEAN_RO=0: the closure pass on every step). The
     // table is the plan's last allocation, so the buffers before it lie where they did
     if (sp.lean && env.lean_ro) {
@@ -1870,6 +1987,13 @@ int pqd_plan_create_multi(pqd_ctx* ctx, int32_t n_sys, const pqd_system* systems
     if (tc.use_trunk && (rc = apply_trunks(P, tc, B, tsys, pt, env, caps, s))) return rc;
     if ((rc = upload_blocks(P, B, tr, sch, s))) return rc;
     const std::vector<int> blk_fast = block_fast_steps(pc.BT, B, E);
+    // rows that stay exactly zero: only the batched sweep's unit list leaves them out. Every other path and the trunk
+    // pre-pass contract all rows, and so does this sweep under PQD_LIVE_ROWS=0
+    P->live.assign(N2, 1);
+    if (pt && env.live_rows != 0 && !pc.split && !pc.msplit && !pc.quad) {
+        P->live = live_row_mask(n_sys, systems, C(rho0), E);
+        P->live_check = env.live_rows == 2;
+    }
 
     // launch parameters
     if ((rc = setup_free_props(P, grid, env, s))) return rc;
@@ -1985,8 +2109,22 @@ int pqd_plan_synchronize(pqd_plan* P) {
     }
     unsigned flags = 0;
     HIPCHK(launch_check_finite(P->out.p, P->out_len, P->flags.p, s));
+    if (P->live_check && P->n_steps > 0) {
+        // PQD_LIVE_ROWS=2: every stored operator is exactly zero from a live column into a dead row (flags bit 1)
+        uint64_t mask = 0;
+        for (int a = 0; a < P->N2; ++a) mask |= (uint64_t)(P->live[a] != 0) << a;
+        const int64_t nM = (int64_t)P->n_sys * 2 * P->n_steps, m2 = (int64_t)P->N2 * P->N2;
+        HIPCHK(launch_check_dead_block(P->M.p, nM, P->N2, mask, P->flags.p, s));
+        for (int y = 0; P->sp.fuse && y < P->n_sys; ++y)  // F(m) exists for 1 <= m < n_steps (FuseParams): F(0) is never written
+            HIPCHK(launch_check_dead_block(P->F.p + ((int64_t)y * P->n_steps + 1) * m2, P->n_steps - 1, P->N2, mask,
+                                           P->flags.p, s));
+        HIPCHK(launch_check_dead_block(P->Midle.p, P->Midle.p ? P->n_sys : 0, P->N2, mask, P->flags.p, s));
+        HIPCHK(launch_check_dead_block(P->Fidle.p, P->Fidle.p ? P->n_sys : 0, P->N2, mask, P->flags.p, s));
+    }
     HIPCHK(hipMemcpyAsync(&flags, P->flags.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    if (flags & 2u)
+        return fail(PQD_ERR_NUMERIC, "PQD_LIVE_ROWS=2: a free propagator couples a live column into a row taken for zero");
     if (flags & 1u) return fail(PQD_ERR_NUMERIC, "non-finite value (NaN/Inf) in the propagated outputs");
     return PQD_OK;
 }
@@ -2135,6 +2273,47 @@ int pqd_plan_describe(const pqd_plan* P, char* buf, int32_t len) {
         sp.split_l2, sp.spin_limit, sp.qprio, sp.ablate, P->fp.packed4, P->fp.mfma, (unsigned long long)P->h_blocks,
         (unsigned long long)P->h_units, (unsigned long long)P->h_groups);
     if (n < 0 || n >= len) return fail(PQD_ERR_ARG, "pqd_plan_describe: the line needs %d bytes, len is %d", n + 1, len);
+    // a plan that leaves rows out says so (bit a of live: row a is contracted); with every row live the line is as it was
+    uint64_t mask = 0;
+    bool dead = false;
+    for (size_t a = 0; a < P->live.size(); ++a) { mask |= (uint64_t)(P->live[a] != 0) << a; dead = dead || !P->live[a]; }
+    if (dead) {
+        const int m = snprintf(buf + n, (size_t)(len - n), " live=%llx parts=%d", (unsigned long long)mask, sp.lean_parts);
+        if (m < 0 || m >= len - n)
+            return fail(PQD_ERR_ARG, "pqd_plan_describe: the line needs %d bytes, len is %d", n + m + 1, len);
+    }
+    return PQD_OK;
+}
+
+int pqd_plan_live_rows(const pqd_plan* P, uint8_t* live, int32_t len) {
+    if (!P || !live) return fail(PQD_ERR_ARG, "NULL argument");
+    const int n = P->hilbert ? P->hp.N * P->hp.N : P->N2;
+    if (len != n) return fail(PQD_ERR_ARG, "pqd_plan_live_rows: len %d, the plan has %d rows", len, n);
+    for (int a = 0; a < n; ++a) live[a] = (size_t)a < P->live.size() ? P->live[a] : 1;
+    return PQD_OK;
+}
+
+int pqd_live_rows(int32_t n_sys, const pqd_system* systems, const pqd_c128* rho0, const pqd_traj* tr, uint8_t* live) {
+    if (!systems || !rho0 || !live) return fail(PQD_ERR_ARG, "NULL argument");
+    if (n_sys < 1) return fail(PQD_ERR_ARG, "n_sys must be >= 1");
+    for (int k = 0; k < n_sys; ++k) {
+        if (int rc = check_system(&systems[k])) return rc;
+        if (systems[k].dim != systems[0].dim)
+            return fail(PQD_ERR_ARG, "system %d: dim %d != %d", k, systems[k].dim, systems[0].dim);
+    }
+    const int N = systems[0].dim;
+    pqd_traj none{};
+    if (!tr) tr = &none;
+    if (tr->n_traj < 0 || tr->n_mto < 0 ||
+        (tr->n_mto > 0 && (!tr->mto_traj || !tr->mto_step || !tr->mto_before || !tr->mto_kind || !tr->mto_ops)))
+        return fail(PQD_ERR_ARG, "bad MTO arrays");
+    for (int q = 0; q < tr->n_mto; ++q) {
+        if (tr->mto_traj[q] < 0 || tr->mto_traj[q] >= tr->n_traj) return fail(PQD_ERR_ARG, "MTO %d: bad trajectory", q);
+        if (tr->mto_kind[q] < 0 || tr->mto_kind[q] > 2) return fail(PQD_ERR_ARG, "MTO %d: kind %d", q, tr->mto_kind[q]);
+    }
+    const MtoEvents E = compose_mtos(N, tr);
+    const std::vector<uint8_t> m = live_row_mask(n_sys, systems, C(rho0), E);
+    std::copy(m.begin(), m.end(), live);
     return PQD_OK;
 }
 

@@ -16,6 +16,20 @@ __global__ __launch_bounds__(256) void check_finite_kernel(const double2* __rest
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flags, 1u);
 }
 
+// PQD_LIVE_ROWS=2: n row-major N2 x N2 operators, bit a of `live` set for the rows the sweep contracts. Any entry
+// [row a not live][column b live] that is not exactly zero (NaN included) sets flags bit 1. Grid-stride over the entries.
+__global__ __launch_bounds__(256) void check_dead_block_kernel(const double2* __restrict__ v, int64_t n_elems, int N2,
+                                                               unsigned long long live, unsigned* __restrict__ flags) {
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_elems; i += (int64_t)gridDim.x * 256) {
+        const int b = (int)(i % N2), a = (int)(i / N2 % N2);
+        if (((live >> a) & 1) || !((live >> b) & 1)) continue;
+        const double2 x = v[i];
+        bad |= !(x.x == 0.0 && x.y == 0.0);
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flags, 2u);
+}
+
 // ACE's output table per trajectory (general_system.py:343, `np.loadtxt(outfile).T`): row 0 the times
 // t_start + dt * step, rows 1 + k the outputs, for the steps of the trajectory's window. One workgroup per trajectory
 // (grid-stride), lanes over steps; the time is dt * step then + t_start in two roundings, as numpy forms it.
@@ -117,6 +131,15 @@ hipError_t launch_table(const double2* out, const long long* woff, const int* wb
     if (n_traj <= 0) return hipSuccess;
     hipLaunchKernelGGL(table_kernel, dim3((unsigned)std::min(n_traj, 1 << 16)), dim3(256), 0, s, out, woff, wbeg,
                        wend, toff, n_traj, n_out, t_start, dt, table);
+    return hipGetLastError();
+}
+
+hipError_t launch_check_dead_block(const double2* v, int64_t n_ops, int N2, unsigned long long live, unsigned* flags,
+                                   hipStream_t s) {
+    if (n_ops <= 0 || !v) return hipSuccess;
+    if (N2 < 1 || N2 > 64) return hipErrorInvalidValue;
+    const int64_t n = n_ops * N2 * N2, blocks = std::min<int64_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(check_dead_block_kernel, dim3((unsigned)blocks), dim3(256), 0, s, v, n, N2, live, flags);
     return hipGetLastError();
 }
 

@@ -451,10 +451,13 @@ struct LeanPt {
     // one unit of R rows: qn holds k-steps 0 .. PF - 1 of its slice Qu on entry and, with MORE, those of the wave's
     // next unit (slice Qnext) on return: the last PF k-steps load them in place of their own slice's.
     // xr, wr: the rows' read and write addresses; avn: k-step 0 of the state rows (issued by the caller)
-    template <int R, bool MORE, typename ST>
+    // NXT > 0: the next unit is a partial one of NXT column groups, Qnext its slice from its first group on; its first
+    // stage is loaded instead (ldq_part below)
+    template <int R, bool MORE, typename ST, int NXT = 0>
     static __device__ __forceinline__ void unit(dbl2 (&qn)[PF][NG], const double2* Qu, const double2* Qnext,
                                                 unsigned qoff, const LdsC2* (&xr)[R][RB], LdsC2* (&wr)[R][RB],
                                                 dbl2 (&avn)[R][RB], const ST& stg) {
+        static_assert(NXT == 0 || (MORE && PF == 1), "a partial successor is loaded one stage ahead");
         double p1[R][RB][NG], p2[R][RB][NG], p3[R][RB][NG];
 #pragma unroll
         for (int ks = 0; ks < KSN; ++ks) {
@@ -467,7 +470,10 @@ struct LeanPt {
 #pragma unroll
                 for (int g = 0; g < NG; ++g) qn[f][g] = qn[f + 1][g];
             if (ks + PF < KSN) ldq(qn[PF - 1], Qu, qoff, ks + PF);
-            else if (MORE) ldq(qn[PF - 1], Qnext, qoff, ks + PF - KSN);
+            else if (MORE) {
+                if constexpr (NXT == 0) ldq(qn[PF - 1], Qnext, qoff, ks + PF - KSN);
+                else ldq_part<NXT>(qn[PF - 1], Qnext, qoff, 0);
+            }
 #pragma unroll
             for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -581,6 +587,193 @@ struct LeanPt {
             e = u1;
         }
         unit_r<false>(qn, Qs, e, e, qoff, xl, wl, Qs, LeanNoStage{});
+    }
+
+    // ---- partial units (SweepParams::lean_parts): plans whose rows that stay zero get no unit deal the remaining rows
+    // in quarters, so a wave's list is [partial unit,] one whole one-row unit (pqd_host.cpp lean_part_units).
+    // A partial unit (slice, row, -1, g0 | NGU << 4) contracts the whole state row with the column groups
+    // g0 .. g0 + NGU - 1 of the slice only (NGU = 1 or 2 of the NG = 4): the same MFMAs with the same operands in the
+    // same k order per accumulator and the same combine as unit(), so its columns are bit-identical to a whole unit's.
+    // It reads only those column groups: a row split over several waves costs no L2 bytes more than a whole one.
+    // So that the pipeline keeps the whole unit's proportions (4 slice loads of 16 B, 24 MFMAs per scheduling region, one
+    // region loaded ahead), a stage is KPS = NG / NGU k-steps of the unit's NGU groups: slot kk NGU + g of the stage
+    // holds group g0 + g of k-step KPS st + kk. A k-step is KSB = 4 KiB on, beyond the load's immediate, so every k-step
+    // of a stage has its own scalar base (scalar adds) and the groups stay in the immediate; the lane offset is qoff.
+    // Bounds: Qp = slice + 16 g0 elements with g0 + NGU <= NG (part_g0 masks the descriptor to that), so a load is
+    // slice + 256 (g0 + g) + KSB ks + qoff with g0 + g < NG and ks < KSN: the addresses unit() loads (static_assert above).
+    // The rows of a split row are read by every wave that holds a part of it and written in place, so no part may be
+    // written before all of them are read: the accumulators stay in registers across a workgroup barrier (run_parts).
+    static_assert(NG == 4, "partial units: quarters of four column groups");
+    template <int NGU>
+    static __device__ __forceinline__ void ldq_part(dbl2 (&q)[NG], const double2* Qp, unsigned qoff, int st) {
+        constexpr int KPS = NG / NGU;
+#pragma unroll
+        for (int kk = 0; kk < KPS; ++kk) {
+            unsigned long long b = (unsigned long long)Qp + (size_t)(KPS * st + kk) * KSB;
+            asm("" : "+s"(b));
+            asm("" : "+v"(qoff));
+            const GlobalBytes* bp = (const GlobalBytes*)b;
+#pragma unroll
+            for (int g = 0; g < NGU; ++g)
+                q[kk * NGU + g] = *(const __attribute__((address_space(1))) dbl2*)(bp + (size_t)qoff + 256 * g);
+        }
+    }
+    // first column group and group count of a partial unit's descriptor, forced into the slice whatever the word holds
+    static __device__ __forceinline__ int part_ng(int4 e) { return (e.w >> 4) == 2 ? 2 : 1; }
+    static __device__ __forceinline__ int part_g0(int4 e) { return part_ng(e) == 2 ? (e.w & 2) : (e.w & 3); }
+
+    // the MFMAs of a partial unit. qn holds its stage 0 on entry and k-step 0 of the whole unit that follows it (slice
+    // Qnext) on return. p1, p2, p3: its accumulators, combined and written by part_write behind the barrier
+    template <int NGU, typename ST>
+    static __device__ __forceinline__ void part(dbl2 (&qn)[PF][NG], const double2* Qp, const double2* Qnext, unsigned qoff,
+                                                const LdsC2* (&xr)[RB], double (&p1)[RB][NGU], double (&p2)[RB][NGU],
+                                                double (&p3)[RB][NGU], const ST& stg) {
+        static_assert(PF == 1, "one stage in flight");
+        constexpr int KPS = NG / NGU, NST = KSN / KPS;
+        dbl2 avn[RB][KPS];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+            for (int kk = 0; kk < KPS; ++kk) avn[rb][kk] = xr[rb][4 * kk];
+#pragma unroll
+        for (int st = 0; st < NST; ++st) {
+            __builtin_amdgcn_sched_barrier(0);
+            dbl2 qv[NG], av[RB][KPS];
+#pragma unroll
+            for (int j = 0; j < NG; ++j) qv[j] = qn[0][j];
+            if (st + 1 < NST) ldq_part<NGU>(qn[0], Qp, qoff, st + 1);
+            else ldq(qn[0], Qnext, qoff, 0);
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+                for (int kk = 0; kk < KPS; ++kk) {
+                    av[rb][kk] = avn[rb][kk];
+                    if (st + 1 < NST) avn[rb][kk] = xr[rb][4 * (KPS * (st + 1) + kk)];
+                }
+            double qs[NG];
+#pragma unroll
+            for (int j = 0; j < NG; ++j) qs[j] = qv[j].x + qv[j].y;
+            if constexpr (ST::ACTIVE) {
+                if (st == 0) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    stg();
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+#pragma unroll
+            for (int kk = 0; kk < KPS; ++kk)
+#pragma unroll
+                for (int rb = 0; rb < RB; ++rb) {
+                    const double as = av[rb][kk].x + av[rb][kk].y;
+                    const bool first = st == 0 && kk == 0;
+#pragma unroll
+                    for (int g = 0; g < NGU; ++g) {
+                        const int j = kk * NGU + g;
+                        p1[rb][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(av[rb][kk].x, qv[j].x, first ? 0.0 : p1[rb][g], 0, 0, 0);
+                        p2[rb][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(av[rb][kk].y, qv[j].y, first ? 0.0 : p2[rb][g], 0, 0, 0);
+                        p3[rb][g] = __builtin_amdgcn_mfma_f64_4x4x4f64(as, qs[j], first ? 0.0 : p3[rb][g], 0, 0, 0);
+                    }
+                }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // every part of a split row has been read (the caller's barrier): combine as unit() does and write the unit's columns
+    template <int NGU>
+    static __device__ __forceinline__ void part_write(LdsC2* (&wr)[RB], const double (&p1)[RB][NGU],
+                                                      const double (&p2)[RB][NGU], const double (&p3)[RB][NGU]) {
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+            for (int g = 0; g < NGU; ++g)
+                wr[rb][16 * g] = dbl2{p1[rb][g] - p2[rb][g], p3[rb][g] - p1[rb][g] - p2[rb][g]};
+    }
+    // The barrier between the partial units' reads and writes. Every wave of the workgroup passes exactly one per PT phase
+    // (a wave without a partial unit at once). The reads have returned (lgkmcnt(0): their values fed MFMAs already, so
+    // nothing is waited for), the slice loads in flight stay in flight: no vmcnt wait, unlike __syncthreads()
+    static __device__ __forceinline__ void part_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+    // a partial unit e of NGU groups with its barrier and write; Qs: the step's slice set; en: the whole unit behind it
+    template <int NGU, typename ST>
+    static __device__ __forceinline__ void part_r(dbl2 (&qn)[PF][NG], const double2* Qs, int4 e, int4 en, unsigned qoff,
+                                                  const double2* xl, double2* wl, const ST& stg) {
+        const int g0 = part_g0(e);
+        const double2* Qp = Qs + (size_t)e.x * CHI * CHI + 16 * g0;
+        const double2* Qnext = Qs + (size_t)en.x * CHI * CHI;
+        const LdsC2* xr[RB];
+        LdsC2* wr[RB];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) {
+            xr[rb] = lds_row((const LdsC2*)xl, e.y, rb);
+            wr[rb] = lds_row((LdsC2*)wl + 16 * g0, e.y, rb);
+        }
+        double p1[RB][NGU], p2[RB][NGU], p3[RB][NGU];
+        part<NGU>(qn, Qp, Qnext, qoff, xr, p1, p2, p3, stg);
+        part_barrier();
+        part_write<NGU>(wr, p1, p2, p3);
+    }
+    // the whole one-row unit e of a wave in a plan with partial units; NXT: what the wave's first unit of the next PT
+    // phase is (0: e itself, a whole unit; 1, 2: a partial unit of that many groups, Qnext its slice from its first group)
+    template <bool MORE, int NXT, typename ST>
+    static __device__ __forceinline__ void whole1(dbl2 (&qn)[PF][NG], const double2* Qu, const double2* Qnext, int row,
+                                                  unsigned qoff, const double2* xl, double2* wl, const ST& stg) {
+        const LdsC2* xr[1][RB];
+        LdsC2* wr[1][RB];
+        dbl2 avn[1][RB];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) {
+            xr[0][rb] = lds_row((const LdsC2*)xl, row, rb);
+            wr[0][rb] = lds_row((LdsC2*)wl, row, rb);
+            avn[0][rb] = xr[0][rb][0];
+        }
+        unit<1, MORE, ST, NXT>(qn, Qu, Qnext, qoff, xr, wr, avn, stg);
+    }
+    // run_pre() for a plan with partial units: u0 is partial (u0.w >= 0) with the whole unit u1 behind it, or whole and
+    // alone, or absent. qn: the first stage of u0 in this step's set Qs on entry, in the next step's set Qn on return
+    template <typename ST>
+    static __device__ __forceinline__ void run_pre_parts(dbl2 (&qn)[PF][NG], const double2* Qs, const double2* Qn, int4 u0,
+                                                         int4 u1, unsigned qoff, const double2* xl, double2* wl, ST stg) {
+        if (u0.x < 0 || u0.w < 0) {
+            part_barrier();
+            if (u0.x < 0) return;
+            const double2* Qu = Qs + (size_t)u0.x * CHI * CHI;
+            whole1<true, 0>(qn, Qu, Qn + (size_t)u0.x * CHI * CHI, u0.y, qoff, xl, wl, stg);
+            return;
+        }
+        const double2* Qu = Qs + (size_t)u1.x * CHI * CHI;
+        const double2* Qnext = Qn + (size_t)u0.x * CHI * CHI + 16 * part_g0(u0);
+        if (part_ng(u0) == 2) {
+            part_r<2>(qn, Qs, u0, u1, qoff, xl, wl, stg);
+            whole1<true, 2>(qn, Qu, Qnext, u1.y, qoff, xl, wl, LeanNoStage{});
+        } else {
+            part_r<1>(qn, Qs, u0, u1, qoff, xl, wl, stg);
+            whole1<true, 1>(qn, Qu, Qnext, u1.y, qoff, xl, wl, LeanNoStage{});
+        }
+    }
+    // the first stage of the wave's first unit u0 in the set Qs (what run_pre_parts expects in qn)
+    static __device__ __forceinline__ void ldq_first_parts(dbl2 (&qn)[PF][NG], const double2* Qs, int4 u0, unsigned qoff) {
+        const double2* Qu = Qs + (size_t)u0.x * CHI * CHI;
+        if (u0.w < 0) ldq(qn[0], Qu, qoff, 0);
+        else if (part_ng(u0) == 2) ldq_part<2>(qn[0], Qu + 16 * part_g0(u0), qoff, 0);
+        else ldq_part<1>(qn[0], Qu + 16 * part_g0(u0), qoff, 0);
+    }
+    // run() for a plan with partial units
+    static __device__ __forceinline__ void run_parts(const double2* Qs, int4 u0, int4 u1, unsigned qoff, const double2* xl,
+                                                     double2* wl) {
+        if (u0.x < 0) {
+            part_barrier();
+            return;
+        }
+        dbl2 qn[PF][NG];
+        ldq_first_parts(qn, Qs, u0, qoff);
+        int4 e = u0;
+        if (u0.w >= 0) {
+            if (part_ng(u0) == 2) part_r<2>(qn, Qs, u0, u1, qoff, xl, wl, LeanNoStage{});
+            else part_r<1>(qn, Qs, u0, u1, qoff, xl, wl, LeanNoStage{});
+            e = u1;
+        } else {
+            part_barrier();
+        }
+        whole1<false, 0>(qn, Qs + (size_t)e.x * CHI * CHI, Qs, e.y, qoff, xl, wl, LeanNoStage{});
     }
 };
 
@@ -870,12 +1063,15 @@ __device__ __forceinline__ void pt_row_mfma16(const double2* __restrict__ Qg, do
 // it reads the outputs inside the fused column operator (LeanCol above; the fast region of the step loop: 184.7 -> 178.9 ms).
 // slice k-steps in flight in the lean instance's PT phase (2 measured the same within the spread and takes all 256 VGPRs)
 constexpr int LEAN_PF = 1;
-template <int N2, int CHI, int BT, bool TRUNK, bool LEAN = false>
+// PARTS: the lean instance for plans whose unit list holds partial units (SweepParams::lean_parts, LeanPt::run_parts);
+// an instance of its own, so that a plan without them runs the code it always ran
+template <int N2, int CHI, int BT, bool TRUNK, bool LEAN = false, bool PARTS = false>
 __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_kernel(SweepParams p, const double2* __restrict__ Mg,
                                                            const double2* __restrict__ Qg0, double2* __restrict__ outg,
                                                            const double2* __restrict__ Fg, const double2* __restrict__ Wg) {
     using L = SweepLayout<N2, CHI, BT>;
     static_assert(!LEAN || (N2 == 16 && CHI == 64 && BT == 8 && !TRUNK), "the lean instance is the headline shape only");
+    static_assert(!PARTS || LEAN, "partial units exist in the lean instance only");
     constexpr int RS = L::RS, TS = L::TS, KD = L::KD, NCOL = L::NCOL;
     constexpr int WPT = L::WPT, NW = L::NW, NT = 64 * NW;  // waves per trajectory, waves, threads
     const int ablate = LEAN ? 0 : p.ablate;
@@ -1045,7 +1241,11 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
                     }
                     // the first k-step of the wave's first unit, in flight from one step's PT phase to the next's
                     typename LP::dbl2 qn[LEAN_PF][CHI / 16];
-                    if (u0.x >= 0) LP::ldq_first(qn, Qg0 + ((size_t)sc_cur * p.D + u0.x) * CHI * CHI, lean_qoff);
+                    if constexpr (PARTS) {
+                        if (u0.x >= 0) LP::ldq_first_parts(qn, Qg0 + (size_t)sc_cur * p.D * CHI * CHI, u0, lean_qoff);
+                    } else {
+                        if (u0.x >= 0) LP::ldq_first(qn, Qg0 + ((size_t)sc_cur * p.D + u0.x) * CHI * CHI, lean_qoff);
+                    }
                     for (; n < n_end - 1; ++n) {
                         sc_nxt = ldc(p.sched + (n + 1 < p.n_steps ? n + 1 : p.n_steps - 1));
                         if (occupied) {
@@ -1072,9 +1272,18 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
                                                               p.closure + (size_t)sc_cur * CHI,
                                                               Wst + (size_t)(n + 1) * p.n_out * N2),
                                                       st_off, st_to, n + 2 < n_end ? st_ln : 0ull};
+                            if constexpr (PARTS)
+                                LP::run_pre_parts(qn, Qg0 + (size_t)sc_cur * p.D * CHI * CHI,
+                                                  Qg0 + (size_t)sc_nxt * p.D * CHI * CHI, u0, u1, lean_qoff, lean_xl, lean_wl, stg);
+                            else
                             LP::run_pre(qn, Qg0 + (size_t)sc_cur * p.D * CHI * CHI, Qg0 + (size_t)sc_nxt * p.D * CHI * CHI, u0,
                                         u1, lean_qoff, lean_xl, lean_wl, stg);
                         } else {
+                            if constexpr (PARTS)
+                                LP::run_pre_parts(qn, Qg0 + (size_t)sc_cur * p.D * CHI * CHI,
+                                                  Qg0 + (size_t)sc_nxt * p.D * CHI * CHI, u0, u1, lean_qoff, lean_xl, lean_wl,
+                                                  LeanNoStage{});
+                            else
                             LP::run_pre(qn, Qg0 + (size_t)sc_cur * p.D * CHI * CHI, Qg0 + (size_t)sc_nxt * p.D * CHI * CHI, u0,
                                         u1, lean_qoff, lean_xl, lean_wl, LeanNoStage{});
                         }
@@ -1222,7 +1431,8 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
         if constexpr (LEAN) {
             // 3M rows of this wave's one or two units (LeanPt above)
             const double2* Qs = Qg0 + (size_t)sc_cur * p.D * CHI * CHI;
-            LeanPt<CHI, RS, TS, LEAN_PF>::run(Qs, u0, u1, lean_qoff, lean_xl, lean_wl);
+            if constexpr (PARTS) LeanPt<CHI, RS, TS, LEAN_PF>::run_parts(Qs, u0, u1, lean_qoff, lean_xl, lean_wl);
+            else LeanPt<CHI, RS, TS, LEAN_PF>::run(Qs, u0, u1, lean_qoff, lean_xl, lean_wl);
         } else if (!(ablate & 1)) {
             const double2* Qs = Qg0 + (size_t)p.sched[n] * p.D * CHI * CHI;
             // pt_mode 0: VALU rows, 1: matrix-core rows (4x4x4_4b), 4: matrix-core rows with 3 real products per
@@ -1419,15 +1629,15 @@ __global__ __launch_bounds__(64) void sweep_nopt_kernel(SweepParams p) {
     }
 }
 
-template <int N2, int CHI, int BT, bool TRUNK, bool LEAN = false>
+template <int N2, int CHI, int BT, bool TRUNK, bool LEAN = false, bool PARTS = false>
 hipError_t launch_sw(int n_blocks, const SweepParams& p, hipStream_t s) {
     using L = SweepLayout<N2, CHI, BT>;
     // the lean instance: the staging area of its fast region behind rbuf (LeanStage; 6 KiB of the 27.8 KiB left)
     constexpr size_t LDS = L::LDS + (LEAN ? LeanStage<BT * L::TS + BT * N2>::BYTES : 0);
     static_assert((BT * L::TS + BT * N2) * sizeof(double2) == L::LDS, "the area starts where the states and rbuf end");
     static_assert(LDS + 512 <= 160 * 1024, "LDS budget (512 B: the kernel's static tables)");
-    if (hipError_t e = allow_dyn_lds<&pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN>>(LDS); e != hipSuccess) return e;
-    hipLaunchKernelGGL((pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN>), dim3(n_blocks), dim3(64 * L::NW), LDS, s, p, p.M,
+    if (hipError_t e = allow_dyn_lds<&pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN, PARTS>>(LDS); e != hipSuccess) return e;
+    hipLaunchKernelGGL((pt_sweep_kernel<N2, CHI, BT, TRUNK, LEAN, PARTS>), dim3(n_blocks), dim3(64 * L::NW), LDS, s, p, p.M,
                        p.Q, p.out, p.F, p.W);
     return hipGetLastError();
 }
@@ -1465,7 +1675,9 @@ hipError_t launch_sweep(int N2, int CHI, int BT, int n_blocks, const SweepParams
         if (BT == 4) return launch_sw_chi<N, 4>(CHI, n_blocks, p, s);
         if constexpr (sw_max_bt(N) == 8) {
             if constexpr (N == 16) {
+                if (p.lean && p.lean_parts && CHI == 64) return launch_sw<16, 64, 8, false, true, true>(n_blocks, p, s);
                 if (p.lean && CHI == 64) return launch_sw<16, 64, 8, false, true>(n_blocks, p, s);
+                if (p.lean_parts) return hipErrorInvalidValue;  // a list with partial units is the lean instance's alone
             }
             return launch_sw_chi<N, 8>(CHI, n_blocks, p, s);
         }

@@ -263,6 +263,25 @@ def propagate(system, grid: Grid, rho0, out_ops: Sequence, traj: Trajectories,
     return split_output(out, traj, len(out_ops))
 
 
+def live_rows(system, rho0, traj: Optional[Trajectories] = None):
+    """The Liouville rows alpha = i N + j that can ever be nonzero (pqd_live_rows; host only, no device): reachable from
+    the nonzero entries of rho0 through L0, the generators of every channel with a nonzero sample, and the MTOs of
+    `traj`; the union over a list of systems. Returns a sorted list of row indices. The batched sweep contracts only
+    these rows with the PT (PQD_LIVE_ROWS)."""
+    systems = _systems(system)
+    N = systems[0].dim
+    if any(s.dim != N for s in systems):
+        raise ValueError("all systems of a batch must have the same dimension")
+    convs = [s.to_c() for s in systems]
+    sc = (_lib.pqd_system * len(systems))(*[c for c, _ in convs])
+    r0 = _c(rho0).reshape(N * N)
+    tc, keep = (None, None) if traj is None else traj.to_c(1, N)[:2]
+    mask = (C.c_uint8 * (N * N))()
+    _lib.check(_lib.lib().pqd_live_rows(len(systems), sc, _lib.cptr(r0), None if tc is None else C.byref(tc), mask))
+    del convs, keep
+    return [a for a in range(N * N) if mask[a]]
+
+
 def table_offsets(traj: Trajectories, n_out):
     """offsets of the per-trajectory ACE tables ((1 + n_out) rows of the window) in a pqd_propagate_table buffer"""
     L = np.asarray(traj.out_end, dtype=np.int64) - np.asarray(traj.out_begin, dtype=np.int64) + 1
@@ -524,10 +543,20 @@ class Plan:
 
     def describe(self):
         """every decision plan creation took (pqd_plan_describe) as a dict of strings: path, workgroup shape, split /
-        quad / trunk layout, windows, the A/B switches, and hashes of the block, row-unit and group tables"""
+        quad / trunk layout, windows, the A/B switches, and hashes of the block, row-unit and group tables. A plan whose
+        sweep leaves out rows that stay zero (live_rows) has two more entries at the end: "live", the mask of the rows it
+        contracts (hex, bit alpha), and "parts", 1 when the lean instance deals them in quarters"""
         buf = C.create_string_buffer(2048)
         _lib.check(_lib.lib().pqd_plan_describe(self.handle, buf, len(buf)))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split())
+
+    def live_rows(self):
+        """the Liouville rows the plan's sweep contracts with the PT, sorted (pqd_plan_live_rows): every row unless the
+        plan runs the batched sweep and some rows stay exactly zero (engine.live_rows; PQD_LIVE_ROWS=0: every row)"""
+        n = self.dim * self.dim
+        mask = (C.c_uint8 * n)()
+        _lib.check(_lib.lib().pqd_plan_live_rows(self.handle, mask, n))
+        return [a for a in range(n) if mask[a]]
 
     def traj_steps(self):
         """trajectory-steps one execute propagates (shared trunks counted once per workgroup)"""
