@@ -375,11 +375,12 @@ int pqd_map_tail(pqd_ctx* ctx, const pqd_c128* M, int32_t N2, const pqd_c128* X,
  * by its persistent grid, not by n_maps. n_maps == 0 returns PQD_OK without touching the device.
  * PQD_ERR_ARG: a NULL argument, n_maps < 0, rcond negative or NaN. PQD_ERR_UNSUPPORTED: n < 1 or n > 576
  * ("map size %d (max 576)"). PQD_ERR_NOMEM: the input maps, the output maps (n_maps n^2 16 bytes each) or
- * the workspace cannot be allocated; the message names the bytes asked for. PQD_ERR_NUMERIC (n >= 37; out
+ * the workspace cannot be allocated; the message names the bytes asked for. PQD_ERR_NUMERIC (every n; out
  * still copied): a map's Jacobi SVD was still rotating after 40 sweeps, or a singular value was not finite.
  * pqd_tl_dynmap_timing: duration (ms, HIP events) of the kernel of the context's last pqd_tl_dynmap_pseudo
  * call (either kernel); PQD_ERR_ARG before any call has completed. pqd_tl_dynmap_sweeps: the largest sweep
- * count over the maps of that call (-1 after the n <= 36 kernel, which does not report it). */
+ * count over the maps of that call (either kernel; the sweeps run, the last one without a rotation; 0 when
+ * n_maps == 1, where no kernel runs). */
 int pqd_tl_dynmap_pseudo(pqd_ctx* ctx, const pqd_c128* dm, int32_t n_maps, int32_t n, double rcond,
                          pqd_c128* out);
 int pqd_tl_dynmap_timing(pqd_ctx* ctx, double* ms_kernel);

@@ -468,7 +468,9 @@ hipError_t launch_propagate_tau(int N2, const double2* dm, const double2* rho0, 
 hipError_t launch_dynamics_t1(const FourTimeParams& p, double2* out, hipStream_t s);
 hipError_t launch_map_tail(int N2, const double2* M, const double2* X, int n_x, const double2* w, int n_steps,
                            double2* out, hipStream_t s);
-hipError_t launch_tl_dynmap(const double2* dm, int n_maps, int n, double rcond, double2* out, hipStream_t s);
+// aux (zeroed by the caller): [0] flags, bit 0 non-finite, bit 1 not converged; [1] the largest sweep count
+hipError_t launch_tl_dynmap(const double2* dm, int n_maps, int n, double rcond, double2* out, unsigned* aux,
+                            hipStream_t s);
 int tl_dynmap_nmax();
 // tlmap_wide.hip: map sizes tl_dynmap_wide_nmin() .. tl_dynmap_wide_nmax(). _plan gives the persistent grid and the
 // workspace (in double2) that _wide wants; flags: bit 0 non-finite, bit 1 not converged; sweeps: the largest count

@@ -188,7 +188,7 @@ struct pqd_ctx {
     double dressed_ms = -1.0;  // kernel duration of the last pqd_dressed_states call (pqd_dressed_timing)
     double dynmap_ms = -1.0;   // duration of the map instance of the last pqd_dynmap_wide call (pqd_dynmap_timing)
     double tlmap_ms = -1.0;    // kernel duration of the last pqd_tl_dynmap_pseudo call (pqd_tl_dynmap_timing)
-    int tlmap_sweeps = -1;     // its largest Jacobi sweep count (tlmap_wide.hip; -1 after the n <= 36 kernel)
+    int tlmap_sweeps = -1;     // its largest Jacobi sweep count (either kernel)
 };
 
 namespace {
@@ -2888,9 +2888,9 @@ int pqd_tl_dynmap_pseudo(pqd_ctx* ctx, const pqd_c128* dm, int32_t n_maps, int32
     if (hipError_t e = o.alloc(total); e != hipSuccess) return nomem(e, "output maps", total);
     if (wide) {
         if (hipError_t e = ws.alloc(ws_elems); e != hipSuccess) return nomem(e, "Jacobi workspace", ws_elems);
-        HIPCHK(aux.alloc(2));
-        HIPCHK(hipMemsetAsync(aux.p, 0, 2 * sizeof(unsigned), s));
     }
+    HIPCHK(aux.alloc(2));
+    HIPCHK(hipMemsetAsync(aux.p, 0, 2 * sizeof(unsigned), s));
     HIPCHK(hipMemcpyAsync(d.p, dm, total * sizeof(double2), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(o.p, d.p, m2 * sizeof(double2), hipMemcpyDeviceToDevice, s));  // out[0] = dm[0]
 
@@ -2907,16 +2907,16 @@ int pqd_tl_dynmap_pseudo(pqd_ctx* ctx, const pqd_c128* dm, int32_t n_maps, int32
             HIPCHK(launch_tl_dynmap_wide(d.p, n_maps, n, rcond, o.p, ws.p, grid, aux.p,
                                          reinterpret_cast<int*>(aux.p + 1), s));
         else
-            HIPCHK(launch_tl_dynmap(d.p, n_maps, n, rcond, o.p, s));
+            HIPCHK(launch_tl_dynmap(d.p, n_maps, n, rcond, o.p, aux.p, s));
         HIPCHK(hipEventRecord(ev[1], s));
-        if (wide) HIPCHK(hipMemcpyAsync(res, aux.p, sizeof res, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(res, aux.p, sizeof res, hipMemcpyDeviceToHost, s));
         touch_pages(out, total * sizeof(double2));
         HIPCHK(hipMemcpyAsync(out, o.p, total * sizeof(double2), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
         ctx->tlmap_ms = ms;
-        ctx->tlmap_sweeps = wide ? (int)res[1] : -1;
+        ctx->tlmap_sweeps = (int)res[1];
         // the maps are handed over all the same (they show where the run went bad)
         if (res[0] & 1u) return fail(PQD_ERR_NUMERIC, "non-finite value (NaN/Inf) in the singular values of a map");
         if (res[0] & 2u)

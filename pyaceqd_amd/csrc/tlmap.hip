@@ -11,7 +11,10 @@
 // A, V and the product stay in LDS (column-major, n <= 36 = N^2 at N = 6). Each Jacobi round
 // rotates n/2 disjoint column pairs (round-robin tournament): lane k computes pair k's Gram
 // entries, then all lanes apply the rotations element-wise.
+// aux (as tlmap_wide.hip reports): aux[0] |= 1 for a non-finite sum of the s_j^2, else |= 2 for a map still rotating
+// when TL_MAX_SWEEPS ended its loop; aux[1] = the largest sweep count (the sweeps run, the last one without a rotation).
 #include "pqd_common.h"
+#include <cfloat>
 
 namespace {
 
@@ -27,7 +30,7 @@ __device__ __forceinline__ void rr_pair(int m, int k, int j, int& p, int& q) {
 }
 
 __global__ __launch_bounds__(64) void tl_dynmap_kernel(const double2* __restrict__ dm, int n, double rcond,
-                                                       double2* __restrict__ out) {
+                                                       double2* __restrict__ out, unsigned* __restrict__ aux) {
     __shared__ double2 A[TL_NMAX * TL_LD], V[TL_NMAX * TL_LD], B[TL_NMAX * TL_LD];
     __shared__ double rc[TL_NMAX / 2 + 1], rs[TL_NMAX / 2 + 1], wsc[TL_NMAX];
     __shared__ double2 rph[TL_NMAX / 2 + 1];
@@ -45,8 +48,13 @@ __global__ __launch_bounds__(64) void tl_dynmap_kernel(const double2* __restrict
     }
     const int m = n + (n & 1);  // odd n: player n is a dummy (its pairs are skipped)
     const int half = m / 2;
-    const double tol = 2.220446049250313e-16 * n;
+    // a pair rotates while |a_p^H a_q| > tol |a_p| |a_q|. What is left below tol goes into the pinv as if it were
+    // zero, n - 1 pairs a column: with tol = n eps a 36 x 36 map of condition 3 came out 11 eps cond from its exact
+    // answer, with 4 eps 1.8 (tests/test_gpu_tlmap_small.py, the semigroup chains), for at most one sweep more
+    const double tol = 2.220446049250313e-16 * (n < 4 ? n : 4);
     __syncthreads();
+    int sweeps = 0;
+    bool conv = false;
     for (int sweep = 0; sweep < TL_MAX_SWEEPS; ++sweep) {
         if (lane == 0) rotated = 0;
         __syncthreads();
@@ -101,7 +109,8 @@ __global__ __launch_bounds__(64) void tl_dynmap_kernel(const double2* __restrict
             }
             __syncthreads();
         }
-        if (!rotated) break;
+        sweeps = sweep + 1;
+        if (!rotated) { conv = true; break; }
         __syncthreads();
     }
     // s_j^2 = |w_j|^2; weights 1/s_j^2 above the cut-off (numpy: s > rcond * max(s))
@@ -114,9 +123,17 @@ __global__ __launch_bounds__(64) void tl_dynmap_kernel(const double2* __restrict
         wsc[lane] = al;
     }
     __syncthreads();
-    double smax2 = 0.0;
-    for (int j = 0; j < n; ++j) smax2 = fmax(smax2, wsc[j]);
+    double smax2 = 0.0, ssum = 0.0;
+    for (int j = 0; j < n; ++j) {
+        smax2 = fmax(smax2, wsc[j]);
+        ssum += wsc[j];
+    }
     const double smax = sqrt(smax2);
+    if (lane == 0) {
+        if (!(ssum <= DBL_MAX)) atomicOr(aux, 1u);   // Inf or NaN
+        else if (!conv) atomicOr(aux, 2u);
+        atomicMax(aux + 1, (unsigned)sweeps);
+    }
     __syncthreads();
     if (lane < n) {
         const double sj = sqrt(wsc[lane]);
@@ -145,8 +162,9 @@ __global__ __launch_bounds__(64) void tl_dynmap_kernel(const double2* __restrict
 
 int tl_dynmap_nmax() { return TL_NMAX; }
 
-hipError_t launch_tl_dynmap(const double2* dm, int n_maps, int n, double rcond, double2* out, hipStream_t s) {
+hipError_t launch_tl_dynmap(const double2* dm, int n_maps, int n, double rcond, double2* out, unsigned* aux,
+                            hipStream_t s) {
     if (n_maps > 1)
-        hipLaunchKernelGGL(tl_dynmap_kernel, dim3(n_maps - 1), dim3(64), 0, s, dm, n, rcond, out);
+        hipLaunchKernelGGL(tl_dynmap_kernel, dim3(n_maps - 1), dim3(64), 0, s, dm, n, rcond, out, aux);
     return hipGetLastError();
 }

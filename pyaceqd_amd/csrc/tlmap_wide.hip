@@ -1,8 +1,9 @@
 // tlmap_wide.hip — time-local dynamical maps for the map sizes above tlmap.hip's single-wave kernel: 37 <= n <= 576
 // (n = N^2 of the cavity and sensor models, N = 7 .. 24; any n in the range is taken, not only perfect squares).
 //   out[0] = dm[0];  out[i] = dm[i] · pinv(dm[i-1], rcond)   for i = 1 .. n_maps-1
-// The method is tlmap.hip's, a one-sided (Hestenes) Jacobi with the same rotations and the same stop rule (a whole
-// sweep without a pair |a_p^H a_q| > n eps |a_p| |a_q|, 40 sweeps at most), applied to the columns of A^H, that is to
+// The method is tlmap.hip's, a one-sided (Hestenes) Jacobi with the same rotations and the same kind of stop rule (a
+// whole sweep without a pair |a_p^H a_q| > n eps |a_p| |a_q|, where tlmap.hip has min(n, 4) eps; 40 sweeps at most),
+// applied to the columns of A^H, that is to
 // the ROWS of A = dm[i-1]: A^H·V = W with orthogonal columns w_j = s_j u_j, so A = V W^H,
 //   pinv(A) = W diag(1/s_j^2) V^H  (s_j > rcond max s, else 0),   out[i] = (dm[i] W) diag(w) V^H;
 // U is never formed, and no Gram matrix or normal equations enter (they would square the condition number and move the

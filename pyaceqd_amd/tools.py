@@ -187,9 +187,9 @@ def calc_tl_dynmap_pseudo(dm, times, debug=False):
     Runs on the GPU (libpqd `pqd_tl_dynmap_pseudo`: one one-sided Jacobi SVD per map, one workgroup each). Map sizes
     n = dm.shape[1] up to 576 (Hilbert dimension up to 24): n <= 36 on the single-wave kernel with the map in LDS,
     37 <= n <= 576 on the block-Jacobi kernel (`csrc/tlmap_wide.hip`); the C side picks. Larger maps
-    raise `PQDError` (unsupported). The reference's LinAlgError retry without rcond has no counterpart: above n = 36
-    a map whose SVD is still rotating after 40 sweeps, or a non-finite singular value, raises `PQDError` (numeric);
-    `debug` is accepted for signature compatibility."""
+    raise `PQDError` (unsupported). The reference's LinAlgError retry without rcond has no counterpart: at every n
+    a map whose SVD is still rotating after 40 sweeps, or a non-finite singular value (a NaN or Inf in dm), raises
+    `_lib.NumericError`, a `PQDError`; `debug` is accepted for signature compatibility."""
     from . import _lib
     dm = np.ascontiguousarray(dm, dtype=np.complex128)
     n_out = len(times) - 1

@@ -11,7 +11,10 @@ def savez_lzma(path, **arrays):
         for name, a in arrays.items():
             buf = io.BytesIO()
             np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
-            z.writestr(name + ".npy", buf.getvalue())
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))   # no clock: same arrays, same file
+            info.compress_type = zipfile.ZIP_LZMA
+            info.external_attr = 0o600 << 16
+            z.writestr(info, buf.getvalue())
 
 
 if __name__ == "__main__":   # recompress existing files in place: python tests/golden/npz_lzma.py FILE.npz ...

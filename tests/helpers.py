@@ -412,3 +412,186 @@ def rabi_system(area_pi=1.0, tau=2.0, t0=10.0, gamma=0.0, dt=0.05, te=20.0):
     lind = [(gamma, ketbra(N, 0, 1))] if gamma else []
     return System(dim=2, H0=np.zeros((2, 2)), lindblad=lind, channels=[(X, f.astype(complex))], sample_t0=0.0,
                   sample_dt=ds), Grid(0.0, dt, n_steps, 1)
+
+
+# ------------------------------------------------------------------ time-local maps: unit of error, inputs, restatement
+# Shared by tests/golden/make_golden_tlmap_truth.py, tests/test_tlmap_truth_host.py and tests/test_gpu_tlmap_small.py.
+EPS = float(np.finfo(np.float64).eps)
+TL_MAX_SWEEPS = 40   # csrc/tlmap.hip
+
+
+def tl_rel(got, ref):
+    """max|got - ref| / max|ref|"""
+    got, ref = np.asarray(got), np.asarray(ref)
+    return float(np.max(np.abs(got - ref)) / np.max(np.abs(ref)))
+
+
+def tl_kept(A, rcond):
+    """numpy's float64 singular values of A (descending) and how many of them numpy's pinv keeps: s > rcond * max(s)"""
+    s = np.linalg.svd(np.asarray(A, dtype=np.complex128), compute_uv=False)
+    return s, int(np.count_nonzero(s > rcond * s[0]))
+
+
+def tl_unit(A, E, T, rcond):
+    """u = eps (|T|_2 |A|_2 + |E|_2) / s_min_kept / max|T|: the first-order change of T = E pinv(A, rcond), relative to
+    its largest entry, under backward errors of size eps |A|_2 in A and eps |E|_2 in E. With dA and dE such errors and
+    P = pinv(A), d(E P) = dE P - E P dA P on the kept subspace, and |P|_2 = 1 / s_min_kept, so
+    |dT|_2 <= eps (|E|_2 + |T|_2 |A|_2) / s_min_kept. s_min_kept is the smallest singular value above rcond * s_max."""
+    s, k = tl_kept(A, rcond)
+    tmax = float(np.max(np.abs(T)))
+    if k == 0 or tmax == 0.0:
+        raise ValueError("no singular value kept, or a zero result: the unit is not defined")
+    return EPS * (np.linalg.norm(T, 2) * s[0] + np.linalg.norm(E, 2)) / s[k - 1] / tmax
+
+
+def tl_near_cut(A, rcond):
+    """True when a singular value of A lies within 1 % of the cut rcond * s_max. A Jacobi singular value carries an
+    absolute error of about eps * s_max, at the cut 1e-12 * s_max a relative one of about 2e-4: whether such a value is
+    kept is not defined, and neither is the result. 1e-2 is 50 times that. numpy's float64 singular values."""
+    s, _ = tl_kept(A, rcond)
+    cut = rcond * s[0]
+    return bool(cut > 0.0 and np.any(np.abs(s - cut) < 1e-2 * cut))
+
+
+def tl_haar(rng, n):
+    return np.linalg.qr(rng.normal(size=(n, n)) + 1j * rng.normal(size=(n, n)))[0]
+
+
+def tl_graded(rng, n, n_maps, cond=1e3, tail=None):
+    """n_maps maps Q1 diag(s) Q2 with fresh Haar-like Q1, Q2 and s log-spaced from 1 to 1 / cond; `tail` replaces the
+    last len(tail) singular values"""
+    dm = np.empty((n_maps, n, n), dtype=np.complex128)
+    for i in range(n_maps):
+        s = np.logspace(0, -np.log10(cond), n)
+        if tail is not None:
+            s[n - len(tail):] = tail
+        dm[i] = (tl_haar(rng, n) * s) @ tl_haar(rng, n)
+    return dm
+
+
+def tl_semigroup_chain(N, seed, n_maps=120, tau=0.5):
+    """(T, dm): T = expm(tau L) and the cumulative maps dm[i] = T^(i+1) of a Lindblad semigroup on N levels (row-major
+    vec, n = N^2). L has a random Hermitian Hamiltonian (normal entries, scaled by 0.5) and the N - 1 decay channels
+    |k><k+1| of rate 1: one stationary state, every other mode decays, so the singular values of dm[i] fall
+    exponentially, cross rcond * s_max one after another, and the kept rank goes from N^2 to 1."""
+    rng = np.random.default_rng(seed)
+    H = rng.normal(size=(N, N)) + 1j * rng.normal(size=(N, N))
+    H = 0.25 * (H + H.conj().T)
+    I = np.eye(N)
+    L = -1j * (np.kron(H, I) - np.kron(I, H.T))
+    for k in range(N - 1):
+        Lk = ketbra(N, k, k + 1)
+        LdL = Lk.conj().T @ Lk
+        L = L + np.kron(Lk, Lk.conj()) - 0.5 * np.kron(LdL, I) - 0.5 * np.kron(I, LdL.T)
+    T = sla.expm(tau * L)
+    dm = np.empty((n_maps, N * N, N * N), dtype=np.complex128)
+    dm[0] = T
+    for i in range(1, n_maps):
+        dm[i] = T @ dm[i - 1]
+    return T, dm
+
+
+def tl_rr_pairs(n):
+    """the column pairs (p < q) of each round of tlmap.hip's round-robin tournament: m = n + (n & 1) players, player
+    m - 1 fixed; round k, slot j pairs (k + j) mod (m - 1) with (k - j) mod (m - 1), slot 0 pairs k with m - 1. For odd
+    n the player n is a dummy whose pairs are left out. One (ps, qs) index pair per round."""
+    m = n + (n & 1)
+    rounds = []
+    for k in range(m - 1):
+        ps, qs = [], []
+        for j in range(m // 2):
+            p, q = (k, m - 1) if j == 0 else ((k + j) % (m - 1), (k - j + (m - 1)) % (m - 1))
+            p, q = min(p, q), max(p, q)
+            if q < n:
+                ps.append(p)
+                qs.append(q)
+        rounds.append((np.array(ps, dtype=int), np.array(qs, dtype=int)))
+    return rounds
+
+
+def tl_tol_factor(n):
+    """csrc/tlmap.hip rotates a pair while |a_p^H a_q| > tl_tol_factor(n) eps |a_p| |a_q|"""
+    return min(n, 4)
+
+
+def _tl_fma(a, b, c):
+    """fma(a, b, c) of float64 arrays: the product and the sum in long double (64-bit mantissa on x86), rounded once
+    more to float64. Not the exact fused result, but like it the rounding error of a b survives when a b and c cancel,
+    which a float64 product does not show."""
+    return (np.asarray(a, dtype=np.longdouble) * b + c).astype(np.float64)
+
+
+def _tl_rotate_fused(X, Y, c, s):
+    """a_p' = c x - s y and a_q' = s x + c y as the kernel's instructions evaluate them: the compiler contracts each
+    component to fma(x, c, -(y s)) and fma(x, s, y c). With x = y and c = s (equal columns) the plain float64 form
+    gives an exact zero, the fused one the rounding error of a product, and the kernel goes on to orthogonalise such
+    residue: a restatement without this expects too few sweeps of rank-deficient maps (6 for 10 at n = 9)."""
+    xr, xi = np.asarray(X.real, dtype=np.longdouble), np.asarray(X.imag, dtype=np.longdouble)
+    yr, yi = Y.real, Y.imag
+    P = (xr * c - yr * s).astype(np.float64) + 1j * (xi * c - yi * s).astype(np.float64)
+    Q = (xr * s + yr * c).astype(np.float64) + 1j * (xi * s + yi * c).astype(np.float64)
+    return P, Q
+
+
+def tl_jacobi_restated(dm, rcond, max_sweeps=TL_MAX_SWEEPS, dtype=np.complex128):
+    """csrc/tlmap.hip in numpy, all maps of the chain at once: out[0] = dm[0], out[i] = dm[i] pinv(dm[i-1], rcond) by
+    the kernel's one-sided Jacobi on the columns of dm[i-1] (same tournament, same rotation test
+    |a_p^H a_q| > min(n, 4) eps |a_p| |a_q|, same rotation, same weights 1 / s_j^2 for s_j > rcond s_max), and the kernel's
+    sweep count per map (sweeps[0] = 0): the sweeps run, the last of them without a rotation, or max_sweeps. Sums run
+    in numpy's order, not the kernel's, and only the rotation of A is evaluated fused (_tl_rotate_fused: it decides
+    the sweep count of rank-deficient maps): results agree with the kernel to rounding, not bit for bit. `dtype` np.clongdouble runs the same steps with that type's eps (for choosing test inputs, not used by a
+    test). Returns (out, sweeps)."""
+    dm = np.asarray(dm, dtype=dtype)
+    n_maps, n = dm.shape[0], dm.shape[1]
+    out = np.empty_like(dm)
+    out[0] = dm[0]
+    sweeps = np.zeros(n_maps, dtype=int)
+    if n_maps < 2:
+        return out, sweeps
+    A = dm[:-1].copy()                                  # (B, n, n), columns A[:, :, j]
+    V = np.broadcast_to(np.eye(n, dtype=dtype), A.shape).copy()
+    tol = np.finfo(dm.real.dtype).eps * tl_tol_factor(n)
+    rounds = tl_rr_pairs(n)
+    live = np.arange(n_maps - 1)                        # the maps that rotated in their last sweep
+    fused = np.dtype(dtype) == np.complex128
+    with np.errstate(all="ignore"):
+        for sweep in range(max_sweeps):
+            Al, Vl = A[live], V[live]
+            rotated = np.zeros(len(live), dtype=bool)
+            for ps, qs in rounds:
+                if len(ps) == 0:
+                    continue
+                X, Y = Al[:, :, ps], Al[:, :, qs]
+                al = np.sum(X.real ** 2 + X.imag ** 2, axis=1)
+                be = np.sum(Y.real ** 2 + Y.imag ** 2, axis=1)
+                g = np.sum(X.conj() * Y, axis=1)
+                ga = np.hypot(g.real, g.imag)
+                act = (ga > tol * np.sqrt(al) * np.sqrt(be)) & (ga > 0.0)
+                if not act.any():
+                    continue
+                rotated |= act.any(axis=1)
+                gs = np.where(act, ga, 1.0)
+                zeta = (be - al) / (2.0 * gs)
+                t = np.where(zeta >= 0.0, 1.0, -1.0) / (np.abs(zeta) + np.sqrt(1.0 + zeta * zeta))
+                c = np.where(act, 1.0 / np.sqrt(1.0 + t * t), 1.0)
+                s = np.where(act, c * t, 0.0)
+                ph = np.where(act, g.conj() / gs, 1.0)  # e^{-i phi}, phi = arg(a_p^H a_q)
+                c, s, ph = c[:, None, :], s[:, None, :], ph[:, None, :]
+                Y = ph * Y
+                if fused:   # on A, which decides the rotations; V only enters the result
+                    Al[:, :, ps], Al[:, :, qs] = _tl_rotate_fused(X, Y, c, s)
+                else:
+                    Al[:, :, ps], Al[:, :, qs] = c * X - s * Y, s * X + c * Y
+                X, Y = Vl[:, :, ps], ph * Vl[:, :, qs]
+                Vl[:, :, ps], Vl[:, :, qs] = c * X - s * Y, s * X + c * Y
+            A[live], V[live] = Al, Vl
+            sweeps[1 + live] = sweep + 1
+            live = live[rotated]                        # a sweep without a rotation ends a map's loop
+            if len(live) == 0:
+                break
+        w2 = np.sum(A.real ** 2 + A.imag ** 2, axis=1)  # (B, n): s_j^2
+        smax = np.sqrt(np.max(w2, axis=1, initial=0.0))
+        w = np.where(np.sqrt(w2) > rcond * smax[:, None], 1.0 / w2, 0.0)
+        Bm = (dm[1:] @ V) * w[:, None, :]
+        out[1:] = Bm @ A.conj().transpose(0, 2, 1)
+    return out, sweeps
