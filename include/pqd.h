@@ -175,7 +175,8 @@ int pqd_dressed_timing(pqd_ctx* ctx, double* ms_kernel);
  * Liouvillian whose norm bound times a sub-step stays below 4096 (PQD_PATH_HILBERT); with a PT of pqd_pt_create_wide
  * dim in [2, 24] equal to the PT's, at most 8 jump operators and the same norm bound at every dim, chi <= 256
  * (PQD_PATH_HILBERT_PT; its workspace of n_traj chi dim^2 16 bytes: PQD_ERR_NOMEM when it cannot be allocated);
- * n_chan <= 4. pqd_pt_create, pqd_free_propagators, pqd_dressed_states and the map-chain calls keep dim <= 6.
+ * n_chan <= 4. pqd_pt_create, pqd_free_propagators, pqd_dressed_states and the map-chain calls keep dim <= 6, except
+ * pqd_calc_onetime_parallel and pqd_propagate_tau, which take dim in [2, 24] (see the map-chain sweeps below).
  * Dynamical maps at dim in [2, 24] come from pqd_dynmap_wide (below), which runs the same two paths. */
 int pqd_propagate(pqd_ctx* ctx, const pqd_system* sys, const pqd_grid* grid, const pqd_pt* pt,
                   const int32_t* sched, const pqd_c128* rho0, int32_t n_out, const pqd_c128* out_ops,
@@ -315,7 +316,14 @@ int pqd_plan_live_rows(const pqd_plan* plan, uint8_t* live, int32_t len);
 int pqd_plan_timing(pqd_plan* plan, double* ms_free, double* ms_sweep, int32_t* n, int32_t reset);
 void pqd_plan_destroy(pqd_plan* plan);
 
-/* ---- map-chain sweeps: reference Fortran signatures, hidden dims explicit, Fortran layouts ---- */
+/* ---- map-chain sweeps: reference Fortran signatures, hidden dims explicit, Fortran layouts ----
+ * Dimension limits (PQD_ERR_UNSUPPORTED outside them): pqd_propagate_tau and pqd_calc_onetime_parallel take dim in
+ * [2, 24] ("dim %d not in [2, 24]"): dim <= 6 on the packed one-wave kernels (mapchain.hip), dim 7..24 on the sweep by
+ * position (mapchain_wide.hip: one matrix-core product per map position for all trajectories in flight; PQD_MC_WIDE=1
+ * sends dim <= 6 there as well). pqd_calc_onetime_parallel_block, pqd_calc_twotime_phonon_block, the time-bin calls and
+ * pqd_map_tail keep dim in [2, 6] ("dim %d not in [2, 6]"; N2 <= 36).
+ * Above dim 6 only the maps the sweep reads are uploaded (max_i j_i - 1 + n_tau of them, n_tau for pqd_propagate_tau);
+ * PQD_ERR_NOMEM, naming the bytes, when the device buffers cannot be allocated. */
 int pqd_propagate_tau(pqd_ctx* ctx, const pqd_c128* dm_tl, int32_t n_maps, const pqd_c128* rho_init,
                       int32_t n_tau, int32_t dim, int32_t j_start, pqd_c128* rho_out);
 /* PQD_ERR_ARG when a trajectory would read a map past dm_tl(:, :, n_tfull - 1) (time_sparse beyond time, or
@@ -325,6 +333,18 @@ int pqd_calc_onetime_parallel(pqd_ctx* ctx, const pqd_c128* dm_tl, const pqd_c12
                               int32_t n_t, int32_t n_tfull, int32_t dim, const pqd_c128* opA,
                               const pqd_c128* opB, const pqd_c128* opC, const double* time,
                               const double* time_sparse, pqd_c128* result);
+/* The schedule of the sweep by position, as pqd_calc_onetime_parallel at dim 7..24 runs it. Host-only: no context, no
+ * device. pos (n_t, may be NULL): the trunk ends p_i = j_i - 1 by the Fortran's comparisons (never decreasing).
+ * *n_rows = Q + 1 with Q = max_i p_i + n_tau. sched (may be NULL; sched_rows rows of 5 int32, PQD_ERR_ARG when fewer
+ * than *n_rows): row q = (live_lo, live_hi, trunk, spawn_lo, spawn_hi): before the step of position q the trajectories
+ * [spawn_lo, spawn_hi), those with p_i == q, start from the trunk state; the step (q < Q) multiplies map q + 1 into
+ * the trajectories [live_lo, live_hi), those with p_i <= q < p_i + n_tau, and into the trunk state when trunk = 1
+ * (q < max_i p_i). Row Q holds spawns only (n_tau = 0).
+ * pqd_mc_wide_timing: duration (ms, HIP events) and number of the kernel launches of the context's last
+ * pqd_calc_onetime_parallel or pqd_propagate_tau call that ran on the sweep by position; PQD_ERR_ARG before one has. */
+int pqd_mc_wide_schedule(const double* time, int32_t n_tfull, const double* time_sparse, int32_t n_t, int32_t n_tau,
+                         int32_t* pos, int32_t* n_rows, int32_t* sched, int32_t sched_rows);
+int pqd_mc_wide_timing(pqd_ctx* ctx, double* ms_kernel, int32_t* launches);
 int pqd_calc_onetime_parallel_block(pqd_ctx* ctx, const pqd_c128* dm_block, const pqd_c128* dm_s,
                                     const pqd_c128* rho_init, int32_t n_tb, int32_t nx_tau, int32_t n_map,
                                     int32_t n_t, int32_t n_tfull, int32_t dim, const pqd_c128* opA,

@@ -124,6 +124,8 @@ _SIGS = {
     "pqd_propagate_tau": ([C.c_void_p, P_C128, C.c_int32, P_C128, C.c_int32, C.c_int32, C.c_int32, P_C128], C.c_int),
     "pqd_calc_onetime_parallel": ([C.c_void_p, P_C128, P_C128, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    P_C128, P_C128, P_C128, P_F64, P_F64, P_C128], C.c_int),
+    "pqd_mc_wide_schedule": ([P_F64, C.c_int32, P_F64, C.c_int32, C.c_int32, P_I32, P_I32, P_I32, C.c_int32], C.c_int),
+    "pqd_mc_wide_timing": ([C.c_void_p, P_F64, P_I32], C.c_int),
     "pqd_calc_onetime_parallel_block": ([C.c_void_p, P_C128, P_C128, P_C128, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, P_C128, P_C128, P_C128, P_F64, P_F64,
                                          P_C128], C.c_int),

@@ -287,6 +287,27 @@ struct MapChainParams {
     double2* X;              // n_blk*n_t*N2: trajectory i's tau state before block c
 };
 
+// map-chain sweep by position for map sizes above one wave (mapchain_wide.hip; n = N2 up to HB_NMAX^2 = 576).
+// One step: Y[:, c] = E X[:, c] for the live columns c of two n x (columns) buffers, each column contiguous.
+struct McwStep {
+    const double2* E;        // the map of this position, n x n column-major
+    const double2* u;        // n: w^T E (mcw_weights_kernel), taken as row n of the map; NULL: no outputs
+    const double2* X;        // read
+    double2* Y;              // written, live columns only
+    const int* pos;          // n_t trunk ends p_i, never decreasing; NULL: every column of [c0, c1) is live
+    double2* result;         // (n_t, n_tau + 1) column-major: row n of column i goes to result[i + (q - p_i + 1) n_t]
+    int n, q, n_tau, n_t;    // q: the position; column i < n_t is live while p_i <= q < p_i + n_tau
+    int c0, c1;              // the live trajectories are inside [c0, c1) (host schedule)
+    int trunk;               // 1: column n_t (the trunk state) is live
+    int cb0;                 // first column block of the grid (set by the launcher)
+};
+struct McwSpawn {            // trajectories i0 .. i0 + gridDim.x - 1 start from the trunk state in column n_t of X
+    const double2 *opA, *opB, *opC;  // Fortran column-major dim x dim
+    double2* X;              // the buffer the step of this position reads
+    double2* result;
+    int dim, n, n_t, i0;
+};
+
 struct FourTimeParams {
     int dim, N2, n_t, n_map, n_precalc;
     double dt, tb;
@@ -462,6 +483,10 @@ int sweep_max_bt(int N2);
 hipError_t launch_sweep_nopt(int N2, int n_blocks, const SweepParams& p, hipStream_t s);
 hipError_t launch_mapchain(const MapChainParams& p, bool pipe, hipStream_t s);  // pipe: the pipelined tau kernel
 hipError_t launch_mapchain_blocked(const MapChainParams& p, int n_chain, hipStream_t s);
+// mapchain_wide.hip: n = 4 .. 576. U[q] = w^T E[q] for Q maps; the spawns of one position; one step (p.cb0 ignored)
+hipError_t launch_mcw_weights(const double2* E, const double2* w, double2* U, int n, int Q, hipStream_t s);
+hipError_t launch_mcw_spawn(const McwSpawn& p, int count, hipStream_t s);
+hipError_t launch_mcw_step(const McwStep& p, hipStream_t s);
 hipError_t launch_four_time(const FourTimeParams& p, hipStream_t s);
 hipError_t launch_propagate_tau(int N2, const double2* dm, const double2* rho0, int n_tau, int j_start,
                                 double2* out, hipStream_t s);

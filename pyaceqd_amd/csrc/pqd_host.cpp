@@ -189,6 +189,8 @@ struct pqd_ctx {
     double dynmap_ms = -1.0;   // duration of the map instance of the last pqd_dynmap_wide call (pqd_dynmap_timing)
     double tlmap_ms = -1.0;    // kernel duration of the last pqd_tl_dynmap_pseudo call (pqd_tl_dynmap_timing)
     int tlmap_sweeps = -1;     // its largest Jacobi sweep count (either kernel)
+    double mcw_ms = -1.0;      // kernel duration of the last wide map-chain call (pqd_mc_wide_timing)
+    int mcw_launches = 0;      // its kernel launches
 };
 
 namespace {
@@ -2508,9 +2510,11 @@ int pqd_fail_msg(int code, const char* msg) { return fail(code, "%s", msg); }
 // =================================================================================================
 // dims of the map-chain, propagate_tau and four-time entry points: one trajectory's Liouville vector fits a wave
 static bool check_dim_2_6(int dim) { return dim >= 2 && dim <= 6; }
+// pqd_calc_onetime_parallel and pqd_propagate_tau: above dim 6 on the sweep by position (mapchain_wide.hip)
+static bool check_dim_2_24(int dim) { return dim >= 2 && dim <= HB_NMAX; }
 
 // The PQD_MC_* switches (in that order), read once per call: tests flip them between calls.
-struct McEnv { bool blocked, pipe, timing; int L; };
+struct McEnv { bool blocked, pipe, timing, wide; int L; };
 static McEnv read_mc_env() {
     auto num = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
     McEnv v;
@@ -2518,6 +2522,7 @@ static McEnv read_mc_env() {
     v.L = num("PQD_MC_L", INT_MIN);             // its block length (raw value; INT_MIN: unset, sqrt(n_tau))
     v.pipe = num("PQD_MC_PIPE", 1) != 0;        // map-by-map tau sweep with the register pipeline (0: mc_tau_kernel)
     v.timing = getenv("PQD_MC_TIMING") != nullptr;  // host-side phase times of the call on stderr
+    v.wide = num("PQD_MC_WIDE", 0) != 0;        // dim 2..6: calc_onetime_parallel and propagate_tau on mapchain_wide.hip
     return v;
 }
 
@@ -2537,9 +2542,12 @@ static std::vector<int> trunk_positions(const MapChainParams& p, const McIn& in)
     return pos;
 }
 
+// mode 0 above dim 6, and below under PQD_MC_WIDE=1: the sweep by position of mapchain_wide.hip
+static bool mc_wide(const MapChainParams& p, const McEnv& env) { return p.mode == 0 && (p.dim > 6 || env.wide); }
+
 // Blocked sweep (mapchain.hip) or map by map: sets `blocked`, and for the blocked sweep pos, p.q_s, p.L, p.Q, p.n_blk
 static int choose_blocked(MapChainParams& p, const McEnv& env, const McIn& in, bool& blocked, std::vector<int>& pos) {
-    blocked = (p.mode == 0 || p.mode == 1) && env.blocked && n2_listed(p.N2);
+    blocked = (p.mode == 0 || p.mode == 1) && env.blocked && n2_listed(p.N2) && !mc_wide(p, env);
     if (p.mode == 0 || blocked) pos = trunk_positions(p, in);
     // mode 0 reads dm_tl(:, :, j_i - 1 + n_tau) at its last tau step, on either set of kernels
     if (p.mode == 0 && (size_t)Q_of(pos, p.n_tau) > in.nA)
@@ -2586,10 +2594,127 @@ static void print_mc_timing(const std::chrono::steady_clock::time_point (&t)[5])
             ms(0, 1), ms(1, 2), ms(2, 3), ms(3, 4));
 }
 
+// ---- the sweep by position (mapchain_wide.hip) ----
+// What the host loop does at position q = 0 .. Q (Q = max_i p_i + n_tau): first the spawns of the trajectories
+// [spawn_lo, spawn_hi) whose trunk ends at q, then (q < Q) one step over the live trajectories [live_lo, live_hi), those
+// with p_i <= q < p_i + n_tau, and over the trunk column while q < max_i p_i. pos never decreases, so both are ranges.
+struct McwPos { int live_lo, live_hi, trunk, spawn_lo, spawn_hi; };
+static std::vector<McwPos> mc_wide_schedule(const std::vector<int>& pos, int n_tau) {
+    const int n_t = (int)pos.size(), Q = Q_of(pos, n_tau), p_max = pos.empty() ? 0 : pos.back();
+    std::vector<McwPos> sch((size_t)Q + 1);
+    int lo = 0, hi = 0;
+    for (int q = 0; q <= Q; ++q) {
+        const int started = hi;
+        while (hi < n_t && pos[hi] <= q) ++hi;
+        while (lo < hi && q - pos[lo] >= n_tau) ++lo;
+        sch[q] = {lo, hi, q < p_max ? 1 : 0, started, hi};
+    }
+    return sch;
+}
+
+// the two events of a timed stretch of the stream
+struct EventPair {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~EventPair() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    hipError_t create() {
+        hipError_t e = hipEventCreate(&ev[0]);
+        return e != hipSuccess ? e : hipEventCreate(&ev[1]);
+    }
+};
+
+// the context's arena with room for `bytes`; PQD_ERR_NOMEM naming them when it cannot grow
+static int mc_arena_reserve(pqd_ctx* ctx, size_t bytes, hipStream_t s) {
+    if (ctx->mc_arena.n >= bytes + 256) return PQD_OK;
+    HIPCHK(hipStreamSynchronize(s));
+    const size_t want = bytes + std::min(bytes / 4, (size_t)64 << 20) + 256;
+    const hipError_t e = ctx->mc_arena.alloc(want);
+    if (e == hipSuccess) return PQD_OK;
+    ctx->mc_arena.release();
+    (void)hipGetLastError();
+    return fail(e == hipErrorOutOfMemory ? PQD_ERR_NOMEM : PQD_ERR_HIP, "map-chain arena of %zu bytes: %s", want,
+                hipGetErrorString(e));
+}
+
+// mode 0 (checked by mapchain_run, pos from choose_blocked): uploads the Q maps the sweep reads, then per position at
+// most one spawn launch and one step launch
+static int mapchain_wide_run(pqd_ctx* ctx, const MapChainParams& p, const McIn& in, const std::vector<int>& pos,
+                             const McEnv& env, pqd_c128* result) {
+    hipStream_t s = ctx->stream;
+    const size_t n = p.N2, m2 = n * n, n_t = p.n_t, nres = n_t * ((size_t)p.n_tau + 1);
+    const int Q = Q_of(pos, p.n_tau);
+    const std::vector<McwPos> sch = mc_wide_schedule(pos, p.n_tau);
+    const size_t ncol = (n_t + 1 + 15) / 16 * 16;  // the trajectories, the trunk state in column n_t, padding
+    // w[r] of Tr(opB R) over the column-major view of R: r = b + a dim gets opB(a, b) (mapchain.hip trace_weight)
+    std::vector<cd> w(n);
+    for (size_t r = 0; r < n; ++r) w[r] = C(in.opB)[r / p.dim + (r % p.dim) * (size_t)p.dim];
+    struct { double2 *E, *U, *w, *opA, *opB, *opC, *X[2], *res; int* pos; } d{};
+    auto carve = [&](Carve& c) {
+        d.E = c.take<double2>((size_t)Q * m2); d.U = c.take<double2>((size_t)Q * n); d.w = c.take<double2>(n);
+        d.opA = c.take<double2>(n); d.opB = c.take<double2>(n); d.opC = c.take<double2>(n);
+        d.X[0] = c.take<double2>(ncol * n); d.X[1] = c.take<double2>(ncol * n);
+        d.res = c.take<double2>(nres); d.pos = c.take<int>(n_t);
+    };
+    Carve sz, cv;
+    carve(sz);
+    if (int rc = mc_arena_reserve(ctx, sz.off, s)) return rc;
+    cv.base = ctx->mc_arena.p;
+    carve(cv);
+    EventPair ev;
+    HIPCHK(ev.create());
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    const decltype(now()) t0 = now();
+    PageToucher toucher((void*)result, nres * sizeof(double2));
+    const size_t vb = n * sizeof(double2);
+    const struct { void* dst; const void* src; size_t bytes; } ups[] = {
+        {d.E, in.dmA, (size_t)Q * m2 * sizeof(double2)}, {d.w, w.data(), vb}, {d.opA, in.opA, vb}, {d.opB, in.opB, vb},
+        {d.opC, in.opC, vb}, {d.X[0] + n_t * n, in.rho_init, vb}, {d.pos, pos.data(), n_t * sizeof(int)}};
+    for (const auto& u : ups)
+        if (u.bytes) HIPCHK(hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    int launches = 0;
+    HIPCHK(hipEventRecord(ev.ev[0], s));
+    if (p.n_tau > 0 && Q > 0) {
+        HIPCHK(launch_mcw_weights(d.E, d.w, d.U, (int)n, Q, s));
+        ++launches;
+    }
+    for (int q = 0; q <= Q; ++q) {
+        const McwPos& r = sch[q];
+        double2 *Xr = d.X[q & 1], *Xw = d.X[(q + 1) & 1];
+        if (r.spawn_hi > r.spawn_lo) {
+            HIPCHK(launch_mcw_spawn({d.opA, d.opB, d.opC, Xr, d.res, p.dim, (int)n, p.n_t, r.spawn_lo},
+                                    r.spawn_hi - r.spawn_lo, s));
+            ++launches;
+        }
+        if (q < Q && (r.live_hi > r.live_lo || r.trunk)) {
+            McwStep st{};
+            st.E = d.E + (size_t)q * m2; st.u = p.n_tau > 0 ? d.U + (size_t)q * n : nullptr;
+            st.X = Xr; st.Y = Xw; st.pos = d.pos; st.result = d.res;
+            st.n = (int)n; st.q = q; st.n_tau = p.n_tau; st.n_t = p.n_t;
+            st.c0 = r.live_lo; st.c1 = r.live_hi; st.trunk = r.trunk;
+            HIPCHK(launch_mcw_step(st, s));
+            ++launches;
+        }
+    }
+    HIPCHK(hipEventRecord(ev.ev[1], s));
+    const auto t1 = now();
+    if (toucher.t.joinable()) toucher.t.join();
+    const auto t2 = now();
+    if (env.timing) HIPCHK(hipStreamSynchronize(s));
+    const auto t3 = now();
+    HIPCHK(hipMemcpyAsync(result, d.res, nres * sizeof(double2), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (env.timing) print_mc_timing({t0, t1, t2, t3, now()});
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]));
+    ctx->mcw_ms = ms;
+    ctx->mcw_launches = launches;
+    return PQD_OK;
+}
+
 static int mapchain_run(pqd_ctx* ctx, MapChainParams& p, const McIn& in, pqd_c128* result) {
     if (!ctx || !in.rho_init || !in.opA || !in.opB || !in.opC || !in.time || !in.time_sparse || !result || !in.dmA)
         return fail(PQD_ERR_ARG, "NULL argument");
-    if (!check_dim_2_6(p.dim)) return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [2, 6]", p.dim);
+    if (p.mode == 0 ? !check_dim_2_24(p.dim) : !check_dim_2_6(p.dim))
+        return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [2, %d]", p.dim, p.mode == 0 ? HB_NMAX : 6);
     if (p.n_t < 1 || p.n_tfull < 1 || p.n_tau < 0) return fail(PQD_ERR_ARG, "bad sizes");
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -2599,6 +2724,7 @@ static int mapchain_run(pqd_ctx* ctx, MapChainParams& p, const McIn& in, pqd_c12
     bool blocked;
     std::vector<int> pos;
     if (int rc = choose_blocked(p, env, in, blocked, pos)) return rc;
+    if (mc_wide(p, env)) return mapchain_wide_run(ctx, p, in, pos, env, result);
     // every device buffer of the call carved from the context's arena
     const size_t N2 = p.N2, m2 = N2 * N2;
     auto carve = [&](Carve& c) {
@@ -2692,15 +2818,48 @@ int pqd_calc_twotime_phonon_block(pqd_ctx* ctx, const pqd_c128* dm_taucs2, const
                                  (size_t)n_map, (size_t)n_map, (size_t)n_tauc * n_map, time, time_sparse}, result);
 }
 
+// pqd_propagate_tau above dim 6 (and below under PQD_MC_WIDE=1): the step kernel of the sweep by position with one
+// column, X = out[:, k] and Y = out[:, k + 1] in place; only the n_tau maps the sweep reads are uploaded
+static int propagate_tau_wide(pqd_ctx* ctx, const pqd_c128* dm_tl, const pqd_c128* rho_init, int n_tau, int N2,
+                              int j_start, pqd_c128* rho_out) {
+    hipStream_t s = ctx->stream;
+    const size_t n = N2, m2 = n * n, nout = n * ((size_t)n_tau + 1);
+    DevBuf<double2> A, o;
+    hipError_t e = A.upload(reinterpret_cast<const double2*>(dm_tl) + (size_t)j_start * m2, (size_t)n_tau * m2, s);
+    if (e == hipSuccess) e = o.alloc(nout);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? PQD_ERR_NOMEM : PQD_ERR_HIP, "maps and states of %zu bytes: %s",
+                    ((size_t)n_tau * m2 + nout) * sizeof(double2), hipGetErrorString(e));
+    HIPCHK(hipMemcpyAsync(o.p, rho_init, n * sizeof(double2), hipMemcpyHostToDevice, s));
+    EventPair ev;
+    HIPCHK(ev.create());
+    HIPCHK(hipEventRecord(ev.ev[0], s));
+    for (int k = 0; k < n_tau; ++k) {
+        McwStep st{};
+        st.E = A.p + (size_t)k * m2; st.X = o.p + (size_t)k * n; st.Y = o.p + (size_t)(k + 1) * n;
+        st.n = N2; st.q = k; st.n_tau = n_tau; st.c0 = 0; st.c1 = 1;
+        HIPCHK(launch_mcw_step(st, s));
+    }
+    HIPCHK(hipEventRecord(ev.ev[1], s));
+    HIPCHK(hipMemcpyAsync(rho_out, o.p, nout * sizeof(double2), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]));
+    ctx->mcw_ms = ms;
+    ctx->mcw_launches = n_tau;
+    return PQD_OK;
+}
+
 int pqd_propagate_tau(pqd_ctx* ctx, const pqd_c128* dm_tl, int32_t n_maps, const pqd_c128* rho_init,
                       int32_t n_tau, int32_t dim, int32_t j_start, pqd_c128* rho_out) {
     if (!ctx || !dm_tl || !rho_init || !rho_out) return fail(PQD_ERR_ARG, "NULL argument");
-    if (!check_dim_2_6(dim)) return fail(PQD_ERR_UNSUPPORTED, "dim %d", dim);
+    if (!check_dim_2_24(dim)) return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [2, %d]", dim, HB_NMAX);
     if (n_tau < 0 || j_start < 0 || j_start + n_tau > n_maps)
         return fail(PQD_ERR_ARG, "maps j_start+1..j_start+n_tau = %d..%d outside 1..%d", j_start + 1, j_start + n_tau, n_maps);
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const int N2 = dim * dim;
+    if (dim > 6 || read_mc_env().wide) return propagate_tau_wide(ctx, dm_tl, rho_init, n_tau, N2, j_start, rho_out);
     DevBuf<double2> A, r0, o;
     HIPCHK(A.upload(reinterpret_cast<const double2*>(dm_tl), (size_t)n_maps * N2 * N2, s));
     HIPCHK(r0.upload(reinterpret_cast<const double2*>(rho_init), N2, s));
@@ -2708,6 +2867,37 @@ int pqd_propagate_tau(pqd_ctx* ctx, const pqd_c128* dm_tl, int32_t n_maps, const
     HIPCHK(launch_propagate_tau(N2, A.p, r0.p, n_tau, j_start, o.p, s));
     HIPCHK(hipMemcpyAsync(rho_out, o.p, (size_t)N2 * (n_tau + 1) * sizeof(double2), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return PQD_OK;
+}
+
+int pqd_mc_wide_schedule(const double* time, int32_t n_tfull, const double* time_sparse, int32_t n_t, int32_t n_tau,
+                         int32_t* pos, int32_t* n_rows, int32_t* sched, int32_t sched_rows) {
+    if (!time || !time_sparse || !n_rows) return fail(PQD_ERR_ARG, "NULL argument");
+    if (n_t < 1 || n_tfull < 1 || n_tau < 0) return fail(PQD_ERR_ARG, "bad sizes");
+    MapChainParams p{};
+    p.n_t = n_t; p.n_tfull = n_tfull; p.n_tau = n_tau;
+    McIn in{};
+    in.time = time; in.time_sparse = time_sparse;
+    const std::vector<int> ps = trunk_positions(p, in);
+    if ((long long)ps.back() + n_tau >= INT_MAX) return fail(PQD_ERR_ARG, "positions do not fit an int");
+    if (pos) std::copy(ps.begin(), ps.end(), pos);
+    const std::vector<McwPos> sch = mc_wide_schedule(ps, n_tau);
+    *n_rows = (int32_t)sch.size();
+    if (!sched) return PQD_OK;
+    if ((size_t)std::max(sched_rows, 0) < sch.size())
+        return fail(PQD_ERR_ARG, "sched holds %d rows, the schedule has %zu", sched_rows, sch.size());
+    for (size_t q = 0; q < sch.size(); ++q) {
+        const int32_t row[5] = {sch[q].live_lo, sch[q].live_hi, sch[q].trunk, sch[q].spawn_lo, sch[q].spawn_hi};
+        std::copy(row, row + 5, sched + 5 * q);
+    }
+    return PQD_OK;
+}
+
+int pqd_mc_wide_timing(pqd_ctx* ctx, double* ms_kernel, int32_t* launches) {
+    if (!ctx || !ms_kernel || !launches) return fail(PQD_ERR_ARG, "NULL argument");
+    if (ctx->mcw_ms < 0) return fail(PQD_ERR_ARG, "no wide map-chain call has completed on this context");
+    *ms_kernel = ctx->mcw_ms;
+    *launches = ctx->mcw_launches;
     return PQD_OK;
 }
 

@@ -2,7 +2,9 @@
 // (n = N^2 of the cavity and sensor models, N = 7 .. 24; any n in the range is taken, not only perfect squares).
 //   out[0] = dm[0];  out[i] = dm[i] · pinv(dm[i-1], rcond)   for i = 1 .. n_maps-1
 // The method is tlmap.hip's, a one-sided (Hestenes) Jacobi with the same rotations and the same kind of stop rule (a
-// whole sweep without a pair |a_p^H a_q| > n eps |a_p| |a_q|, where tlmap.hip has min(n, 4) eps; 40 sweeps at most),
+// whole sweep without a pair |a_p^H a_q| > sqrt(n) eps |a_p| |a_q| (LAPACK zgesvj's threshold; n eps until the maps'
+// consumer, mapchain_wide.hip, showed its 1.4e-14 at n = 64 in the correlations), where tlmap.hip has min(n, 4) eps;
+// 40 sweeps at most),
 // applied to the columns of A^H, that is to
 // the ROWS of A = dm[i-1]: A^H·V = W with orthogonal columns w_j = s_j u_j, so A = V W^H,
 //   pinv(A) = W diag(1/s_j^2) V^H  (s_j > rcond max s, else 0),   out[i] = (dm[i] W) diag(w) V^H;
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(TW_THREADS) void tl_dynmap_wide_kernel(TlWideParams
     double2* __restrict__ V = W + m2;
     double2* __restrict__ Bm = V + m2;
     const int nb = (n + B - 1) / B;     // column blocks; the last may be short
-    const double tol = 2.220446049250313e-16 * n;
+    const double tol = 2.220446049250313e-16 * sqrt((double)n);
 
     for (int i = blockIdx.x + 1; i < p.n_maps; i += gridDim.x) {
         const double2* __restrict__ Ai = p.dm + (size_t)(i - 1) * m2;   // row-major dm[i-1] = column-major conj(A^H)

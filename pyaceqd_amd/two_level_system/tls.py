@@ -18,7 +18,8 @@ hbar = constants.hbar
 temp_dir = constants.temp_dir
 
 _FWD = ("trajectories", "n_sub", "device", "pulse_sampling", "trapz", "dressed_rho", "lower_only", "wide_pt",
-        "wide_maps", "calc_dynmap", "get_M_t")  # the last two: for the wrappers whose signature lacks them
+        "wide_maps", "calc_dynmap", "get_M_t", "rho0")  # the last three: for the wrappers whose signature lacks them
+# (rho0: the tl_* correlation sweeps hand every system their rho0; the cavity and sensor wrappers used to drop it)
 
 
 def tls(t_start, t_end, *pulses, dt=0.1, gamma_e=1/100, phonons=False, t_mem=6.4, ae=5.0, temperature=4,
