@@ -291,6 +291,75 @@ __device__ __forceinline__ void pt_row_mfma(const double2* __restrict__ Qg, doub
         for (int g = 0; g < NG; ++g) wr[(4 * rb + kk) * TS + 16 * g] = make_double2(cr[rb][g], ci[rb][g]);
 }
 
+// The same row on the VALU: lane l = 16 q + j accumulates input quarter q (bond indices 4 kk + q) of the KD = CHI / 16
+// output columns j + 16 i of every trajectory, then the quarters are summed across the lanes.
+template <int CHI, int BT, int RS, int TS, int KD>
+__device__ __forceinline__ void pt_row_valu(const double2* __restrict__ Qg, double2* st, int a, int lane) {
+    const int pj = lane & 15, pq = lane >> 4;
+    Qg += pj;
+    const double2* xr = st + a * RS + pq;
+    double2 acc[BT][KD];
+#pragma unroll
+    for (int b = 0; b < BT; ++b)
+#pragma unroll
+        for (int i = 0; i < KD; ++i) acc[b][i] = c_zero();
+    double2 qn[KD];
+#pragma unroll
+    for (int i = 0; i < KD; ++i) qn[i] = Qg[(size_t)pq * CHI + 16 * i];
+#pragma unroll 2
+    for (int kk = 0; kk < CHI / 4; ++kk) {
+        double2 qv[KD];
+#pragma unroll
+        for (int i = 0; i < KD; ++i) qv[i] = qn[i];
+        if (kk + 1 < CHI / 4) {
+            const int dn = 4 * (kk + 1) + pq;
+#pragma unroll
+            for (int i = 0; i < KD; ++i) qn[i] = Qg[(size_t)dn * CHI + 16 * i];
+        }
+#pragma unroll
+        for (int b = 0; b < BT; ++b) {
+            const double2 x = xr[b * TS + 4 * kk];
+#pragma unroll
+            for (int i = 0; i < KD; ++i) c_fma(acc[b][i], x, qv[i]);
+        }
+    }
+    // reduce the 4 input quarters (lanes j, j+16, j+32, j+48) and scatter the columns
+    double2* wr = st + a * RS + pj;
+    if constexpr (KD == 4) {
+        const bool q0 = pq & 1, q1 = (pq >> 1) & 1;
+#pragma unroll
+        for (int b = 0; b < BT; ++b) {
+            double2 h[2];
+#pragma unroll
+            for (int pi = 0; pi < 2; ++pi) {
+                const double2 mine = q0 ? acc[b][2 * pi + 1] : acc[b][2 * pi];
+                const double2 oth = q0 ? acc[b][2 * pi] : acc[b][2 * pi + 1];
+                h[pi] = c_add(mine, c_shfl_xor(oth, 16));
+            }
+            const double2 mine = q1 ? h[1] : h[0];
+            const double2 oth = q1 ? h[0] : h[1];
+            wr[b * TS + 16 * pq] = c_add(mine, c_shfl_xor(oth, 32));
+        }
+    } else if constexpr (KD == 2) {
+        const bool q0 = pq & 1;
+#pragma unroll
+        for (int b = 0; b < BT; ++b) {
+            const double2 mine = q0 ? acc[b][1] : acc[b][0];
+            const double2 oth = q0 ? acc[b][0] : acc[b][1];
+            double2 h = c_add(mine, c_shfl_xor(oth, 16));
+            h = c_add(h, c_shfl_xor(h, 32));
+            if (pq < 2) wr[b * TS + 16 * pq] = h;
+        }
+    } else {
+#pragma unroll
+        for (int b = 0; b < BT; ++b) {
+            double2 h = c_add(acc[b][0], c_shfl_xor(acc[b][0], 16));
+            h = c_add(h, c_shfl_xor(h, 32));
+            if (pq == 0) wr[b * TS] = h;
+        }
+    }
+}
+
 // pt_row_mfma with three real products per complex product (3M, see col_apply_mfma3): 3 MFMA chains per
 // (row block, column group) instead of 4; (Qr + Qi) and (Xr + Xi) are one VALU add per loaded element.
 // PF = how many k-steps of the PT slice are in flight ahead of the MFMAs (L2 latency hiding).
@@ -1047,6 +1116,59 @@ __device__ __forceinline__ void pt_row_mfma16(const double2* __restrict__ Qg, do
             wr[(lk + 4 * r) * TS + 16 * t] = make_double2(p1[t][r] - p2[t][r + 2], p2[t][r] + p1[t][r + 2]);
 }
 
+// PT phase of the general instances: this wave's rows of every trajectory times the slices of the set Qs.
+// pt_mode 0: VALU rows, 1: matrix-core rows (4x4x4_4b), 4: matrix-core rows with 3 real products per
+// complex product (default), 3: split-complex 16x16x4 rows (BT = 8), 2: mixed (waves 0..NW/2-1 start on the matrix cores,
+// the others on the VALU, alternating per row), so the two FP64 pipes of a SIMD run concurrently.
+//
+// SweepParams is taken by value: with a reference the instances <25, 64, 4> and <25, 64, 4, TRUNK> gain one VGPR
+// spill each (profiles/r26/sweep_steps/README.md).
+template <int N2, int CHI, int BT>
+__device__ __forceinline__ void pt_phase(SweepParams p, const double2* Qs, double2* st, int wave, int lane) {
+    using L = SweepLayout<N2, CHI, BT>;
+    constexpr int RS = L::RS, TS = L::TS, WPT = L::WPT, NW = L::NW;
+    int parity = (p.pt_mode == 2) ? ((wave >= NW / 2) ? 1 : 0) : 0;
+    if (p.units && (p.pt_mode == 4 || p.pt_mode == 5)) {
+        // 3M rows by the host's per-wave unit list: (slice, row 0, row 1 or -1, rows 2 | 3 << 16 or -1)
+        const int4* U = p.units + (size_t)wave * p.umax;
+        for (int u = 0; u < p.umax; ++u) {
+            const int4 e = U[u];
+            if (e.x < 0) break;
+            const double2* Qg = Qs + (size_t)e.x * CHI * CHI;
+            if (p.pt_mode == 5) pt_rows3<N2, CHI, BT, RS, TS, 2>(Qg, st, e, lane);
+            else pt_rows3<N2, CHI, BT, RS, TS, 1>(Qg, st, e, lane);
+        }
+        return;
+    }
+    for (int a = wave; a < N2; a += NW) {
+        const double2* Qg = Qs + (size_t)p.gmap[a] * CHI * CHI;
+        const bool use_mfma = (p.pt_mode == 1) || (p.pt_mode == 2 && parity == 0);
+        parity ^= 1;
+        if (p.pt_mode == 4) {
+            pt_row_mfma3<CHI, BT, RS, TS, 1>(Qg, st, a, a, a, a, lane);
+            continue;
+        }
+        if (p.pt_mode == 5) {   // 3M with two k-steps of the slice in flight
+            pt_row_mfma3<CHI, BT, RS, TS, 2>(Qg, st, a, a, a, a, lane);
+            continue;
+        }
+        if constexpr (BT == 8) {
+            if (p.pt_mode == 3) {
+                pt_row_mfma16<CHI, RS, TS>(Qg, st, a, lane);
+                continue;
+            }
+        }
+        // the VALU rows are compiled for BT = 4, chi <= 64 and one wave per trajectory only: elsewhere
+        // their accumulators cap the whole kernel's VGPR allocation and spill, so those run modes 0/2 on
+        // the 4x4x4 path
+        if (BT == 8 || CHI > 64 || WPT > 1 || use_mfma || p.pt_mode == 3) {
+            pt_row_mfma<CHI, BT, RS, TS>(Qg, st, a, lane);
+            continue;
+        }
+        if constexpr (BT == 4 && CHI <= 64 && WPT == 1) pt_row_valu<CHI, BT, RS, TS, L::KD>(Qg, st, a, lane);
+    }
+}
+
 // TRUNK: the trunk pre-pass instance (writes checkpoints through p.ck_map); kept out of the main sweep's instance,
 // where the extra live values cost VGPR spills
 // Reads every half step's M, F, W as stored: plans running this kernel (main sweep or trunk pre-pass) build the free
@@ -1072,7 +1194,7 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
     using L = SweepLayout<N2, CHI, BT>;
     static_assert(!LEAN || (N2 == 16 && CHI == 64 && BT == 8 && !TRUNK), "the lean instance is the headline shape only");
     static_assert(!PARTS || LEAN, "partial units exist in the lean instance only");
-    constexpr int RS = L::RS, TS = L::TS, KD = L::KD, NCOL = L::NCOL;
+    constexpr int RS = L::RS, TS = L::TS, NCOL = L::NCOL;
     constexpr int WPT = L::WPT, NW = L::NW, NT = 64 * NW;  // waves per trajectory, waves, threads
     const int ablate = LEAN ? 0 : p.ablate;
     extern __shared__ __attribute__((aligned(16))) double2 smem[];
@@ -1434,112 +1556,7 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
             if constexpr (PARTS) LeanPt<CHI, RS, TS, LEAN_PF>::run_parts(Qs, u0, u1, lean_qoff, lean_xl, lean_wl);
             else LeanPt<CHI, RS, TS, LEAN_PF>::run(Qs, u0, u1, lean_qoff, lean_xl, lean_wl);
         } else if (!(ablate & 1)) {
-            const double2* Qs = Qg0 + (size_t)p.sched[n] * p.D * CHI * CHI;
-            // pt_mode 0: VALU rows, 1: matrix-core rows (4x4x4_4b), 4: matrix-core rows with 3 real products per
-            // complex product (default), 3: split-complex 16x16x4 rows (BT = 8), 2: mixed (waves 0..NW/2-1 start on the matrix cores,
-            // the others on the VALU, alternating per row), so the two FP64 pipes of a SIMD run concurrently
-            int parity = (p.pt_mode == 2) ? ((wave >= NW / 2) ? 1 : 0) : 0;
-            if (p.units && (p.pt_mode == 4 || p.pt_mode == 5)) {
-                // 3M rows by the host's per-wave unit list: (slice, row 0, row 1 or -1, rows 2 | 3 << 16 or -1)
-                const int4* U = p.units + (size_t)wave * p.umax;
-                for (int u = 0; u < p.umax; ++u) {
-                    const int4 e = U[u];
-                    if (e.x < 0) break;
-                    const double2* Qg = Qs + (size_t)e.x * CHI * CHI;
-                    if (p.pt_mode == 5) pt_rows3<N2, CHI, BT, RS, TS, 2>(Qg, st, e, lane);
-                    else pt_rows3<N2, CHI, BT, RS, TS, 1>(Qg, st, e, lane);
-                }
-            } else
-            for (int a = wave; a < N2; a += NW) {
-                const double2* Qg = Qs + (size_t)p.gmap[a] * CHI * CHI;
-                const bool use_mfma = (p.pt_mode == 1) || (p.pt_mode == 2 && parity == 0);
-                parity ^= 1;
-                if (p.pt_mode == 4) {
-                    pt_row_mfma3<CHI, BT, RS, TS, 1>(Qg, st, a, a, a, a, lane);
-                    continue;
-                }
-                if (p.pt_mode == 5) {   // 3M with two k-steps of the slice in flight
-                    pt_row_mfma3<CHI, BT, RS, TS, 2>(Qg, st, a, a, a, a, lane);
-                    continue;
-                }
-                if constexpr (BT == 8) {
-                    if (p.pt_mode == 3) {
-                        pt_row_mfma16<CHI, RS, TS>(Qg, st, a, lane);
-                        continue;
-                    }
-                }
-                // the VALU rows are compiled for BT = 4, chi <= 64 and one wave per trajectory only: elsewhere
-                // their accumulators cap the whole kernel's VGPR allocation and spill, so those run modes 0/2 on
-                // the 4x4x4 path
-                if (BT == 8 || CHI > 64 || WPT > 1 || use_mfma || p.pt_mode == 3) {
-                    pt_row_mfma<CHI, BT, RS, TS>(Qg, st, a, lane);
-                    continue;
-                }
-                if constexpr (BT == 4 && CHI <= 64 && WPT == 1) {
-                Qg += pj;
-                const double2* xr = st + a * RS + pq;
-                double2 acc[BT][KD];
-#pragma unroll
-                for (int b = 0; b < BT; ++b)
-#pragma unroll
-                    for (int i = 0; i < KD; ++i) acc[b][i] = c_zero();
-                double2 qn[KD];
-#pragma unroll
-                for (int i = 0; i < KD; ++i) qn[i] = Qg[(size_t)pq * CHI + 16 * i];
-#pragma unroll 2
-                for (int kk = 0; kk < CHI / 4; ++kk) {
-                    double2 qv[KD];
-#pragma unroll
-                    for (int i = 0; i < KD; ++i) qv[i] = qn[i];
-                    if (kk + 1 < CHI / 4) {
-                        const int dn = 4 * (kk + 1) + pq;
-#pragma unroll
-                        for (int i = 0; i < KD; ++i) qn[i] = Qg[(size_t)dn * CHI + 16 * i];
-                    }
-#pragma unroll
-                    for (int b = 0; b < BT; ++b) {
-                        const double2 x = xr[b * TS + 4 * kk];
-#pragma unroll
-                        for (int i = 0; i < KD; ++i) c_fma(acc[b][i], x, qv[i]);
-                    }
-                }
-                // reduce the 4 input quarters (lanes j, j+16, j+32, j+48) and scatter the columns
-                double2* wr = st + a * RS + pj;
-                if constexpr (KD == 4) {
-                    const bool q0 = pq & 1, q1 = (pq >> 1) & 1;
-#pragma unroll
-                    for (int b = 0; b < BT; ++b) {
-                        double2 h[2];
-#pragma unroll
-                        for (int pi = 0; pi < 2; ++pi) {
-                            const double2 mine = q0 ? acc[b][2 * pi + 1] : acc[b][2 * pi];
-                            const double2 oth = q0 ? acc[b][2 * pi] : acc[b][2 * pi + 1];
-                            h[pi] = c_add(mine, c_shfl_xor(oth, 16));
-                        }
-                        const double2 mine = q1 ? h[1] : h[0];
-                        const double2 oth = q1 ? h[0] : h[1];
-                        wr[b * TS + 16 * pq] = c_add(mine, c_shfl_xor(oth, 32));
-                    }
-                } else if constexpr (KD == 2) {
-                    const bool q0 = pq & 1;
-#pragma unroll
-                    for (int b = 0; b < BT; ++b) {
-                        const double2 mine = q0 ? acc[b][1] : acc[b][0];
-                        const double2 oth = q0 ? acc[b][0] : acc[b][1];
-                        double2 h = c_add(mine, c_shfl_xor(oth, 16));
-                        h = c_add(h, c_shfl_xor(h, 32));
-                        if (pq < 2) wr[b * TS + 16 * pq] = h;
-                    }
-                } else {
-#pragma unroll
-                    for (int b = 0; b < BT; ++b) {
-                        double2 h = c_add(acc[b][0], c_shfl_xor(acc[b][0], 16));
-                        h = c_add(h, c_shfl_xor(h, 32));
-                        if (pq == 0) wr[b * TS] = h;
-                    }
-                }
-                }  // VALU rows
-            }
+            pt_phase<N2, CHI, BT>(p, Qg0 + (size_t)p.sched[n] * p.D * CHI * CHI, st, wave, lane);
         }
         __syncthreads();
 

@@ -13,6 +13,13 @@ split kernels' schedule reader crosses its 64-entry chunk boundary twice. The ca
 pt_split_kernel and pt_msplit_kernel (named in the case id), their switches, and one case per N2 of the batched sweep,
 the quad kernel and the free propagators (the launch layer's dispatch).
 
+The batched sweep itself (pt_sweep.hip; case ids sweep_*, PQD_SPLIT=0 PQD_MSPLIT=0 PQD_QUAD=0): the lean instance with one
+system, two systems in a workgroup, PQD_LEAN_STAGE=0 and PQD_LEAN_RO=0 (19 trajectories, 60 steps, every MTO in the first
+14), with partial units and PQD_LIVE_PART=0, the general instance at that shape, PQD_PT_MODE 0-5 at BT 4 and 8 and the
+VALU rows at chi 16, 32 and 64, PQD_FUSE=0, PQD_TRPRE=0, PQD_CMUL3=0, PQD_COLBIG at N2 = 25 and 36, chi = 128, shared
+trunks from the pre-pass (PQD_TRUNK=1) and from a slot of the workgroup, and chi = 1 at every N2 (sweep_nopt_kernel).
+For these the saved text also holds sweep_lean(), sweep_readout() and sweep_stage().
+
 The map-chain family (mapchain.hip; case ids mc_* and ft_*, e.g. --only mc_,ft_): the three sweep modes at dims 2-6 on
 the default path, with PQD_MC_BLOCKED=0, with PQD_MC_BLOCKED=0 PQD_MC_PIPE=0 and (modes 0, 1) with PQD_MC_L=8;
 propagate_tau and map_tail at dims 2-6; four_time_8op with its three flag settings, four_time and dynamics_t1 at dims
@@ -35,9 +42,59 @@ sys.path.insert(0, HERE)
 N_STEPS = 150
 SWITCHES = ("PQD_SPLIT", "PQD_SPLIT_GRAN", "PQD_SPLIT_OW", "PQD_SPLIT_XCD", "PQD_SPLIT_L2", "PQD_SPLIT_SPIN",
             "PQD_MSPLIT", "PQD_MS_L2", "PQD_MS_PTM", "PQD_MS_TB", "PQD_ABLATE", "PQD_FPM", "PQD_QUAD",
-            "PQD_MC_BLOCKED", "PQD_MC_PIPE", "PQD_MC_L", "PQD_MC_TIMING")
+            "PQD_MC_BLOCKED", "PQD_MC_PIPE", "PQD_MC_L", "PQD_MC_TIMING",
+            "PQD_BT", "PQD_PT_MODE", "PQD_CMUL3", "PQD_COLBIG", "PQD_TRPRE", "PQD_FUSE", "PQD_SWEEP_LEAN", "PQD_LEAN_RO",
+            "PQD_LEAN_STAGE", "PQD_LIVE_PART", "PQD_LIVE_ROWS", "PQD_TRUNK", "PQD_BRANCH")
 SPLIT, MSPLIT = "split groups", "split groups, several trajectories per group"
 BATCHED, QUAD = "batched lock-step sweep", "register-resident TLS quads"
+NOPT = "no PT (one wave per trajectory)"
+
+
+def _sweep_cases(c):
+    """the batched sweep (pt_sweep.hip): every instance kind and switch of pt_sweep_kernel, and sweep_nopt_kernel.
+    `want`: what the child asserts of the plan besides its path (lean instance, readout in the column phase, staging
+    workgroups, partial units), so that a case that left the path it is here for fails"""
+    sw = dict(PQD_SPLIT=0, PQD_MSPLIT=0, PQD_QUAD=0)
+    lean = dict(N=4, chi=64, n_traj=19, late=60)
+    on = dict(lean=True, readout=True)
+    c["sweep_lean_one_system"] = ("pt", dict(lean, want=dict(on, stage=True)), dict(sw, PQD_BT=8), BATCHED)
+    # trajectories are packed by system (10 and 9): the second of the three workgroups mixes the two and does not stage
+    c["sweep_lean_two_systems"] = ("pt", dict(lean, n_sys=2, want=dict(on, stage=True, staging=2)), dict(sw, PQD_BT=8),
+                                   BATCHED)
+    c["sweep_lean_stage=0"] = ("pt", dict(lean, want=dict(on, stage=False)), dict(sw, PQD_BT=8, PQD_LEAN_STAGE=0), BATCHED)
+    c["sweep_lean_ro=0"] = ("pt", dict(lean, want=dict(lean=True, readout=False)), dict(sw, PQD_BT=8, PQD_LEAN_RO=0),
+                            BATCHED)
+    c["sweep_lean=0"] = ("pt", dict(lean, want=dict(lean=False)), dict(sw, PQD_BT=8, PQD_SWEEP_LEAN=0), BATCHED)
+    live = dict(N=4, chi=64, live="x_only")
+    c["sweep_lean_parts"] = ("pt", dict(live, want=dict(lean=True, parts="1")), dict(sw, PQD_BT=8), BATCHED)
+    c["sweep_lean_parts_live_part=0"] = ("pt", dict(live, want=dict(lean=True, parts="0")),
+                                         dict(sw, PQD_BT=8, PQD_LIVE_PART=0), BATCHED)
+    # the general instances' PT rows: modes 0-5 (PQD_SWEEP_LEAN=0: mode 4 is the default and would run the lean instance);
+    # mode 0 at BT = 4 runs the VALU rows with 4, 1 and 2 columns per lane (chi = 64, 16, 32)
+    g = dict(N=4, chi=64, n_traj=9, want=dict(lean=False))
+    for bt in (4, 8):
+        for m in range(6):
+            c[f"sweep_N2=16_chi=64_bt={bt}_ptmode={m}"] = ("pt", g, dict(sw, PQD_BT=bt, PQD_PT_MODE=m, PQD_SWEEP_LEAN=0),
+                                                          BATCHED)
+    c["sweep_N2=4_chi=16_bt=4_ptmode=0"] = ("pt", dict(N=2, chi=16, n_traj=9), dict(sw, PQD_BT=4, PQD_PT_MODE=0), BATCHED)
+    c["sweep_N2=9_chi=32_bt=4_ptmode=0"] = ("pt", dict(N=3, chi=32, n_traj=9), dict(sw, PQD_BT=4, PQD_PT_MODE=0), BATCHED)
+    for s in ("PQD_FUSE", "PQD_TRPRE", "PQD_CMUL3"):
+        c[f"sweep_N2=16_chi=64_bt=8_{s[4:].lower()}=0"] = ("pt", g, dict(sw, PQD_BT=8, **{s: 0}), BATCHED)
+    for N in (5, 6):
+        c[f"sweep_N2={N * N}_chi=32_colbig=0"] = ("pt", dict(N=N, chi=32, n_traj=9), dict(sw, PQD_COLBIG=0), BATCHED)
+        c[f"sweep_N2={N * N}_chi=32_colbig=default"] = ("pt", dict(N=N, chi=32, n_traj=9), sw, BATCHED)
+    c["sweep_N2=16_chi=128_bt=4"] = ("pt", dict(N=4, chi=128, n_traj=9), dict(sw, PQD_BT=4), BATCHED)
+    # shared trunks: the pre-pass instance and activations from its checkpoints, activations from a slot of the workgroup
+    for N, chi, bt in ((4, 64, 8), (3, 16, 4)):
+        # trunks: the plan has trunk pre-pass launches; shared: it propagates fewer trajectory-steps than full runs would
+        br = dict(N=N, chi=chi, branch=29)
+        c[f"sweep_N2={N * N}_chi={chi}_bt={bt}_trunk=1"] = ("pt", dict(br, want=dict(trunks=True)),
+                                                           dict(sw, PQD_BT=bt, PQD_TRUNK=1), BATCHED)
+        c[f"sweep_N2={N * N}_chi={chi}_bt={bt}_trunk=0_branch=1"] = (
+            "pt", dict(br, want=dict(trunks=False, branch="1", shared=True)),
+            dict(sw, PQD_BT=bt, PQD_TRUNK=0, PQD_BRANCH=1), BATCHED)
+    for N in (2, 3, 4, 5, 6):   # no PT: MTOs before and after an output at one step (_trajectories, k = 2)
+        c[f"sweep_nopt_N2={N * N}"] = ("pt", dict(N=N, chi=1, n_traj=9), sw, NOPT)
 
 
 def _cases():
@@ -78,6 +135,7 @@ def _cases():
         c[f"free_N2={N * N}_fpm=0"] = ("free", dict(N=N), dict(PQD_FPM=0), None)
     for chi in (16, 32, 64):
         c[f"quad_N2=4_chi={chi}"] = ("pt", dict(N=2, chi=chi, n_traj=9), dict(PQD_SPLIT=0, PQD_QUAD=2), QUAD)
+    _sweep_cases(c)
     # the map-chain family
     mc_env = {"default": {}, "noblocked": dict(PQD_MC_BLOCKED=0), "noblocked_nopipe": dict(PQD_MC_BLOCKED=0, PQD_MC_PIPE=0),
               "L=8": dict(PQD_MC_L=8)}
@@ -125,6 +183,46 @@ def _trajectories(N, n_traj, seed):
         elif k == 4:
             mt += [MTO(t, s, False, 0, A), MTO(t, min(e, s + 1), False, 1, np.eye(N) * 0.5 + B)]
     return Trajectories(np.array(beg), np.array(end), mt)
+
+
+def _late_trajectories(N, n_traj, n_sys, n_steps):
+    """every MTO in the first 14 steps, ragged windows to the end, one window that opens after its MTO
+    (tests/test_gpu_sweep_readout.py trajectories): the lean instance's fast region runs for most of the steps"""
+    from pyaceqd_amd.engine import MTO, Trajectories
+    rng = np.random.default_rng(100 + n_traj)
+    A = rng.normal(size=(N, N)) + 1j * rng.normal(size=(N, N))
+    B = rng.normal(size=(N, N)) + 1j * rng.normal(size=(N, N))
+    A, B = A / np.linalg.norm(A), B / np.linalg.norm(B)
+    t1 = [1 + (5 * i) % 14 for i in range(n_traj)]
+    mt = [m for i in range(n_traj) for m in (MTO(i, t1[i], False, 2, A), MTO(i, t1[i], False, 1, B))]
+    beg = [t1[i] + 6 if i == 2 else t1[i] for i in range(n_traj)]
+    end = [n_steps - (3 * i) % 11 for i in range(n_traj)]
+    return Trajectories(np.array(beg), np.array(end), mt, system=np.arange(n_traj) % n_sys if n_sys > 1 else None)
+
+
+def _branching_trajectories(N, n_traj, n_sys, n_steps, seed):
+    """trajectories that share their MTO-free start (a two-time sweep: trajectory i branches off at t1_i and runs to the
+    end), with an applyBefore MTO, a second later MTO, MTO-free ones, MTOs at step 0, a window that opens before the MTO
+    and one that ends early (tests/test_gpu_branching.py g2_reuse_shape)"""
+    from pyaceqd_amd.engine import MTO, Trajectories
+    rng = np.random.default_rng(seed)
+    A = rng.normal(size=(N, N)) + 1j * rng.normal(size=(N, N))
+    B = rng.normal(size=(N, N)) + 1j * rng.normal(size=(N, N))
+    A, B = A / np.linalg.norm(A), B / np.linalg.norm(B)
+    beg, end, mt = [], [], []
+    for i in range(n_traj):
+        t1, kind = int(i * (n_steps - 2) / max(1, n_traj - 1)), i % 7
+        if kind == 3:
+            mt.append(MTO(i, max(t1, 1), True, 0, A))
+        elif kind == 6:
+            mt += [MTO(i, 0, False, 2, A), MTO(i, 0, False, 1, B)]
+        elif kind != 5:
+            mt += [MTO(i, t1, False, 2, A), MTO(i, t1, False, 1, B)]
+            if kind == 4:
+                mt.append(MTO(i, min(n_steps, t1 + 3), False, 1, B))
+        beg.append(max(0, t1 - 2) if kind == 2 else t1)
+        end.append(n_steps if kind != 1 else max(t1, n_steps - 4))
+    return Trajectories(np.array(beg), np.array(end), mt, system=np.arange(n_traj) % n_sys if n_sys > 1 else None)
 
 
 def _schedule(n_slices, seed):
@@ -202,16 +300,41 @@ def _child(case, out):
     else:
         chi = p["chi"]
         n_traj = p.get("n_traj", max(1, min(7, 256 // (N * N + 1))))  # every group resident
-        systems = [H.random_system(N, n_steps=N_STEPS, seed=40 + k)[0] for k in range(3)]
-        grid = Grid(0.0, 0.1, N_STEPS)
-        tr = _trajectories(N, n_traj, seed=N + chi)
-        tr.system = np.array([k % 3 for k in range(n_traj)])
-        pt = ptmod.random_pt(N, chi, D=min(N * N, 9), n_slices=9, seed=chi + N, eps=0.05)
-        sched = _schedule(9, seed=chi + 7 * N)
-        pt.schedule = lambda n_steps: np.ascontiguousarray(sched[:n_steps])
         ops = [H.ketbra(N, 0, 0), H.ketbra(N, 1, 0), np.eye(N)]
-        plan = engine.Plan(systems, grid, H.random_rho(N), ops, tr, pt=pt)
-        desc = " ".join(f"{k}={v}" for k, v in sorted(plan.describe().items()))
+        rho0 = H.random_rho(N)
+        if "live" in p:
+            # a drive that leaves Liouville rows exactly zero (tests/test_gpu_live_rows.py), four outputs
+            import dataclasses
+            from tests import live_rows_cases
+            systems, grid, rho0, ops, tr, _ = live_rows_cases.build(p["live"], 4)
+            # one slice per row in a shuffled order, 5 slice sets
+            pt = ptmod.random_pt(N, chi, D=N * N, n_slices=5, seed=chi + 16, eps=0.12)
+            pt = dataclasses.replace(pt, gmap=np.random.default_rng(chi).permutation(N * N).astype(np.int32))
+        elif "late" in p or "branch" in p:
+            n_steps = p.get("late", 36)
+            n_sys = p.get("n_sys", 1 if "late" in p else 2)
+            systems = [H.random_system(N, n_steps=n_steps, seed=80 + k)[0] for k in range(n_sys)]
+            grid = Grid(0.0, 0.1, n_steps)
+            if n_sys == 1:
+                systems = systems[0]
+            if "late" in p:
+                tr = _late_trajectories(N, n_traj, n_sys, n_steps)
+            else:
+                tr = _branching_trajectories(N, p["branch"], n_sys, n_steps, seed=N + chi)
+            pt = ptmod.random_pt(N, chi, D=min(N * N, 9), n_slices=12, seed=chi + N, eps=0.12)
+        else:
+            systems = [H.random_system(N, n_steps=N_STEPS, seed=40 + k)[0] for k in range(3)]
+            grid = Grid(0.0, 0.1, N_STEPS)
+            tr = _trajectories(N, n_traj, seed=N + chi)
+            tr.system = np.array([k % 3 for k in range(n_traj)])
+            pt = None
+            if chi > 1:
+                pt = ptmod.random_pt(N, chi, D=min(N * N, 9), n_slices=9, seed=chi + N, eps=0.05)
+                sched = _schedule(9, seed=chi + 7 * N)
+                pt.schedule = lambda n_steps: np.ascontiguousarray(sched[:n_steps])
+        plan = engine.Plan(systems, grid, rho0, ops, tr, pt=pt)
+        d = plan.describe()
+        desc = " ".join(f"{k}={v}" for k, v in sorted(d.items()))
         plan.execute()
         for t, a in enumerate(plan.download()):
             res[f"out{t:03d}"] = a
@@ -219,6 +342,14 @@ def _child(case, out):
         if want is not None and path != want:
             raise SystemExit(f"{case}: ran on '{path}', not on '{want}'")
         res["info"] = np.array(f"path={path} bt={bt} split_fallbacks={fb}")
+        if path == BATCHED:
+            sw = dict(lean=plan.sweep_lean(), readout=plan.sweep_readout(), stage=plan.sweep_stage())
+            res["info"] = np.array(f"{res['info']} " + " ".join(f"{k}={int(v)}" for k, v in sw.items()))
+            sw.update(stage=sw["stage"] > 0, staging=sw["stage"], parts=d.get("parts", "0"), branch=d["branch"],
+                      trunks=int(d["n_trunk"]) > 0, shared=plan.traj_steps() < int(np.sum(tr.out_end + 1)))
+            bad = {k: (sw[k], v) for k, v in p.get("want", {}).items() if sw[k] != v}
+            if bad:
+                raise SystemExit(f"{case}: (found, wanted) {bad}")
         res["describe"] = np.array(desc)
     np.savez(out, **res)
 
