@@ -341,7 +341,8 @@ int pqd_calc_onetime_parallel(pqd_ctx* ctx, const pqd_c128* dm_tl, const pqd_c12
  * the trajectories [live_lo, live_hi), those with p_i <= q < p_i + n_tau, and into the trunk state when trunk = 1
  * (q < max_i p_i). Row Q holds spawns only (n_tau = 0).
  * pqd_mc_wide_timing: duration (ms, HIP events) and number of the kernel launches of the context's last
- * pqd_calc_onetime_parallel or pqd_propagate_tau call that ran on the sweep by position; PQD_ERR_ARG before one has. */
+ * pqd_calc_onetime_parallel, pqd_calc_onetime_parallel_block_wide or pqd_propagate_tau call that ran on the sweep by
+ * position; PQD_ERR_ARG before one has. */
 int pqd_mc_wide_schedule(const double* time, int32_t n_tfull, const double* time_sparse, int32_t n_t, int32_t n_tau,
                          int32_t* pos, int32_t* n_rows, int32_t* sched, int32_t sched_rows);
 int pqd_mc_wide_timing(pqd_ctx* ctx, double* ms_kernel, int32_t* launches);
@@ -350,6 +351,26 @@ int pqd_calc_onetime_parallel_block(pqd_ctx* ctx, const pqd_c128* dm_block, cons
                                     int32_t n_t, int32_t n_tfull, int32_t dim, const pqd_c128* opA,
                                     const pqd_c128* opB, const pqd_c128* opC, const double* time,
                                     const double* time_sparse, pqd_c128* result);
+/* The periodic sweep at dim in [2, 24] ("dim %d not in [2, 24]"), always as the sweep by position of mapchain_wide.hip;
+ * arguments, NULL and size checks of pqd_calc_onetime_parallel_block, which itself keeps dim in [2, 6] (PQD_MC_WIDE
+ * does not reach it). Two map cursors: the trunk and the trajectories whose trunk ends at p_i >= n_tb follow the
+ * straight one (dm_block(:, :, q + 1) while q < n_map, dm_s after), those with p_i < n_tb the ring one (the same rule
+ * at q mod n_tb); a position where the two name different maps still costs one step launch. Only the block maps the
+ * call reads and dm_s are uploaded: the device footprint does not grow with the number of positions (PQD_ERR_NOMEM
+ * names the bytes). pqd_mc_wide_timing reports the call.
+ * pqd_mc_wide_block_schedule: the schedule that call walks. Host-only, as pqd_mc_wide_schedule: pos, *n_rows = Q + 1
+ * with Q = max_i p_i + n_tb nx_tau, sched rows of 9 int32 (ring_lo, ring_hi, ring_map, str_lo, str_hi, trunk, str_map,
+ * spawn_lo, spawn_hi): the step of position q multiplies map ring_map into the trajectories [ring_lo, ring_hi) (inside
+ * [0, n_ring), n_ring = the number of p_i < n_tb) and map str_map into [str_lo, str_hi) (inside [n_ring, n_t)) and,
+ * when trunk = 1, into the trunk state. A map index m < n_map is dm_block(:, :, m + 1), m = n_map is dm_s. */
+int pqd_calc_onetime_parallel_block_wide(pqd_ctx* ctx, const pqd_c128* dm_block, const pqd_c128* dm_s,
+                                         const pqd_c128* rho_init, int32_t n_tb, int32_t nx_tau, int32_t n_map,
+                                         int32_t n_t, int32_t n_tfull, int32_t dim, const pqd_c128* opA,
+                                         const pqd_c128* opB, const pqd_c128* opC, const double* time,
+                                         const double* time_sparse, pqd_c128* result);
+int pqd_mc_wide_block_schedule(const double* time, int32_t n_tfull, const double* time_sparse, int32_t n_t,
+                               int32_t n_tb, int32_t nx_tau, int32_t n_map, int32_t* pos, int32_t* n_rows,
+                               int32_t* sched, int32_t sched_rows);
 /* n_tauc = 0 is the Fortran's empty loop over the per-trajectory maps: dm_taucs2 is not read and may be NULL */
 int pqd_calc_twotime_phonon_block(pqd_ctx* ctx, const pqd_c128* dm_taucs2, const pqd_c128* dm_sep1,
                                   const pqd_c128* dm_sep2, const pqd_c128* dm_s, const pqd_c128* rho_init,

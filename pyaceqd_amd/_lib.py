@@ -129,6 +129,11 @@ _SIGS = {
     "pqd_calc_onetime_parallel_block": ([C.c_void_p, P_C128, P_C128, P_C128, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, P_C128, P_C128, P_C128, P_F64, P_F64,
                                          P_C128], C.c_int),
+    "pqd_calc_onetime_parallel_block_wide": ([C.c_void_p, P_C128, P_C128, P_C128, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_int32, P_C128, P_C128, P_C128, P_F64, P_F64,
+                                              P_C128], C.c_int),
+    "pqd_mc_wide_block_schedule": ([P_F64, C.c_int32, P_F64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P_I32, P_I32,
+                                    P_I32, C.c_int32], C.c_int),
     "pqd_calc_twotime_phonon_block": ([C.c_void_p, P_C128, P_C128, P_C128, P_C128, P_C128, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P_C128, P_C128,
                                        P_C128, P_F64, P_F64, P_C128], C.c_int),

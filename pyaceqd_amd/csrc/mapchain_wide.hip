@@ -15,6 +15,10 @@
 //                       and the tau start C rho A into column i (formulas and association of mapchain.hip's
 //                       trunk_outputs).
 //   mcw_step_kernel     Y[:, c] = E[q] X[:, c] for the live columns, complex FP64 on v_mfma_f64_16x16x4_f64.
+//   mcw_step2_kernel    the same step for the periodic sweep (calc_onetime_parallel_block, propagate_tau.f90:189-295),
+//                       where the trajectories follow one of two map cursors (pqd_host.cpp mc_wide_block_schedule): at a
+//                       position where the cursors name different maps, the two products in one launch. u is then w^T E
+//                       per uploaded map, not per position.
 // X and Y are ping-pong buffers of n x (columns), each column contiguous. A column that is not live at q (not started,
 // finished, padding) is loaded as zero and writes nothing, so whatever the buffers hold there never moves.
 #include "pqd_common.h"
@@ -42,14 +46,14 @@ __device__ __forceinline__ bool mcw_live(const McwStep& p, int c) {
 // The map tile (64 rows x 16 k) and the X tile (16 k x 32 columns) of a chunk go through LDS: the X tile serves the
 // four row tiles of the workgroup, a wave's map fragment its two column tiles. The next chunk's global loads are issued
 // before the products of the current one. Rows >= n (+1 with u), k >= n and dead columns are zeros by guarded loads.
-__global__ __launch_bounds__(MCW_THREADS) void mcw_step_kernel(McwStep p) {
+__device__ __forceinline__ void mcw_step(const McwStep& p, int by) {
     __shared__ double2 As[MCW_BK * MCW_LDA];
     __shared__ double2 Xs[MCW_BK * MCW_LDB];
     __shared__ int live[MCW_BN];
     __shared__ int any;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
     const int n = p.n;
-    const int r0 = blockIdx.x * MCW_BM, cb = (p.cb0 + blockIdx.y) * MCW_BN;
+    const int r0 = blockIdx.x * MCW_BM, cb = (p.cb0 + by) * MCW_BN;
     if (tid == 0) any = 0;
     __syncthreads();
     if (tid < MCW_BN) {
@@ -122,6 +126,19 @@ __global__ __launch_bounds__(MCW_THREADS) void mcw_step_kernel(McwStep p) {
     }
 }
 
+__global__ __launch_bounds__(MCW_THREADS) void mcw_step_kernel(McwStep p) { mcw_step(p, blockIdx.y); }
+
+// Two families at one position (the periodic sweep, calc_onetime_parallel_block): blockIdx.z picks the family, each
+// with its own map, u row, column range and trunk flag over the same X, Y and result. A family's live columns lie
+// inside its [c0, c1) (mcw_live), so a 32-column tile that straddles the border between the families is issued in
+// both, and in each the other family's columns load zero and write nothing.
+__global__ __launch_bounds__(MCW_THREADS) void mcw_step2_kernel(McwStep2 p) {
+    const int z = blockIdx.z;
+    if ((int)blockIdx.y >= (z ? p.ncb1 : p.ncb0)) return;  // the same in every thread
+    if (z) mcw_step(p.f1, blockIdx.y);
+    else mcw_step(p.f0, blockIdx.y);
+}
+
 // U[q][k] = sum_r w[r] E[q][r + k n]: one wave per map column, lanes over the rows, then a butterfly whose order is
 // fixed (the same bits on every run)
 __global__ __launch_bounds__(MCW_THREADS) void mcw_weights_kernel(const double2* __restrict__ E,
@@ -191,18 +208,37 @@ hipError_t launch_mcw_spawn(const McwSpawn& p, int count, hipStream_t s) {
     return hipGetLastError();
 }
 
-// the grid covers the column blocks from the first live trajectory (or the trunk column) to the last live column;
-// blocks in between without a live column return at once
-hipError_t launch_mcw_step(const McwStep& p0, hipStream_t s) {
-    McwStep p = p0;
+// the column blocks from the first live trajectory (or the trunk column) to the last live column: sets p.cb0 and
+// returns their number (0: nothing live, -1: bad arguments); blocks in between without a live column return at once
+static int mcw_blocks(McwStep& p) {
     const bool traj = p.c0 < p.c1;
-    if (p.n < 1 || p.n > MCW_NMAX || p.c0 < 0 || (p.pos && p.c1 > p.n_t)) return hipErrorInvalidValue;
-    if (!traj && !p.trunk) return hipSuccess;
+    if (p.n < 1 || p.n > MCW_NMAX || p.c0 < 0 || (p.pos && p.c1 > p.n_t)) return -1;
+    if (!traj && !p.trunk) return 0;
     const int first = traj ? p.c0 / MCW_BN : p.n_t / MCW_BN;
     const int last = p.trunk ? p.n_t / MCW_BN : (p.c1 - 1) / MCW_BN;
     p.cb0 = first;
-    const int rows = p.n + (p.u ? 1 : 0);
-    const dim3 grid((rows + MCW_BM - 1) / MCW_BM, last - first + 1);
-    hipLaunchKernelGGL(mcw_step_kernel, grid, dim3(MCW_THREADS), 0, s, p);
+    return last - first + 1;
+}
+static unsigned mcw_row_tiles(const McwStep& p) { return (unsigned)((p.n + (p.u ? 1 : 0) + MCW_BM - 1) / MCW_BM); }
+
+hipError_t launch_mcw_step(const McwStep& p0, hipStream_t s) {
+    McwStep p = p0;
+    const int ncb = mcw_blocks(p);
+    if (ncb < 0) return hipErrorInvalidValue;
+    if (ncb == 0) return hipSuccess;
+    hipLaunchKernelGGL(mcw_step_kernel, dim3(mcw_row_tiles(p), ncb), dim3(MCW_THREADS), 0, s, p);
+    return hipGetLastError();
+}
+
+// one launch for the two families of a position; a family with nothing live leaves the launch to the other
+hipError_t launch_mcw_step2(const McwStep& a, const McwStep& b, hipStream_t s) {
+    McwStep2 p{a, b, 0, 0};
+    p.ncb0 = mcw_blocks(p.f0);
+    p.ncb1 = mcw_blocks(p.f1);
+    if (p.ncb0 < 0 || p.ncb1 < 0 || a.n != b.n || !a.u != !b.u) return hipErrorInvalidValue;
+    if (p.ncb0 == 0) return launch_mcw_step(b, s);
+    if (p.ncb1 == 0) return launch_mcw_step(a, s);
+    const dim3 grid(mcw_row_tiles(a), std::max(p.ncb0, p.ncb1), 2);
+    hipLaunchKernelGGL(mcw_step2_kernel, grid, dim3(MCW_THREADS), 0, s, p);
     return hipGetLastError();
 }

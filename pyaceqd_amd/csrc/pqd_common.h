@@ -301,6 +301,10 @@ struct McwStep {
     int trunk;               // 1: column n_t (the trunk state) is live
     int cb0;                 // first column block of the grid (set by the launcher)
 };
+struct McwStep2 {            // two families of one position in one launch (mcw_step2_kernel)
+    McwStep f0, f1;
+    int ncb0, ncb1;          // column blocks of each family's grid (set by the launcher)
+};
 struct McwSpawn {            // trajectories i0 .. i0 + gridDim.x - 1 start from the trunk state in column n_t of X
     const double2 *opA, *opB, *opC;  // Fortran column-major dim x dim
     double2* X;              // the buffer the step of this position reads
@@ -487,6 +491,7 @@ hipError_t launch_mapchain_blocked(const MapChainParams& p, int n_chain, hipStre
 hipError_t launch_mcw_weights(const double2* E, const double2* w, double2* U, int n, int Q, hipStream_t s);
 hipError_t launch_mcw_spawn(const McwSpawn& p, int count, hipStream_t s);
 hipError_t launch_mcw_step(const McwStep& p, hipStream_t s);
+hipError_t launch_mcw_step2(const McwStep& a, const McwStep& b, hipStream_t s);
 hipError_t launch_four_time(const FourTimeParams& p, hipStream_t s);
 hipError_t launch_propagate_tau(int N2, const double2* dm, const double2* rho0, int n_tau, int j_start,
                                 double2* out, hipStream_t s);

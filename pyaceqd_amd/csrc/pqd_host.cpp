@@ -2612,6 +2612,25 @@ static std::vector<McwPos> mc_wide_schedule(const std::vector<int>& pos, int n_t
     return sch;
 }
 
+// The periodic sweep (calc_onetime_parallel_block, propagate_tau.f90:189-295) by position. Two map cursors: the straight
+// one, dm_block(:, :, q + 1) while q < n_map and dm_s after, is followed by the trunk and by the trajectories whose
+// trunk ends at p_i >= n_tb (their j never meets the wrap test j == n_tb + 1, :285); the ring one, the same rule at
+// q mod n_tb, by the trajectories with p_i < n_tb. pos never decreases, so the ring trajectories are [0, n_ring) and
+// the live range of mc_wide_schedule splits at n_ring into one range per cursor. Map index n_map stands for dm_s.
+struct McwBlockPos { int ring_lo, ring_hi, ring_map, str_lo, str_hi, trunk, str_map, spawn_lo, spawn_hi; };
+static std::vector<McwBlockPos> mc_wide_block_schedule(const std::vector<int>& pos, int n_tb, int n_tau, int n_map) {
+    const std::vector<McwPos> one = mc_wide_schedule(pos, n_tau);
+    const int n_ring = (int)(std::lower_bound(pos.begin(), pos.end(), n_tb) - pos.begin());
+    std::vector<McwBlockPos> sch(one.size());
+    for (size_t q = 0; q < one.size(); ++q) {
+        const McwPos& r = one[q];
+        sch[q] = {std::min(r.live_lo, n_ring), std::min(r.live_hi, n_ring), std::min((int)(q % (size_t)n_tb), n_map),
+                  std::max(r.live_lo, n_ring), std::max(r.live_hi, n_ring), r.trunk,
+                  (int)std::min(q, (size_t)n_map), r.spawn_lo, r.spawn_hi};
+    }
+    return sch;
+}
+
 // the two events of a timed stretch of the stream
 struct EventPair {
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -2635,21 +2654,24 @@ static int mc_arena_reserve(pqd_ctx* ctx, size_t bytes, hipStream_t s) {
                 hipGetErrorString(e));
 }
 
-// mode 0 (checked by mapchain_run, pos from choose_blocked): uploads the Q maps the sweep reads, then per position at
-// most one spawn launch and one step launch
+// The driver of both sweeps by position: uploads the n_up maps of `maps` that the schedule reads and then `last` (dm_s;
+// NULL in mode 0) as map n_up, then per position at most one spawn launch and one step launch. A map index of the
+// schedule below n_up is that map, any other is `last`. The device footprint is n_up + 1 maps, two state buffers and
+// the result: it does not grow with the number of positions.
 static int mapchain_wide_run(pqd_ctx* ctx, const MapChainParams& p, const McIn& in, const std::vector<int>& pos,
-                             const McEnv& env, pqd_c128* result) {
+                             const std::vector<McwBlockPos>& sch, const pqd_c128* maps, size_t n_up,
+                             const pqd_c128* last, const McEnv& env, pqd_c128* result) {
     hipStream_t s = ctx->stream;
     const size_t n = p.N2, m2 = n * n, n_t = p.n_t, nres = n_t * ((size_t)p.n_tau + 1);
-    const int Q = Q_of(pos, p.n_tau);
-    const std::vector<McwPos> sch = mc_wide_schedule(pos, p.n_tau);
+    const int Q = (int)sch.size() - 1;
+    const size_t n_dev = n_up + (last ? 1 : 0);
     const size_t ncol = (n_t + 1 + 15) / 16 * 16;  // the trajectories, the trunk state in column n_t, padding
     // w[r] of Tr(opB R) over the column-major view of R: r = b + a dim gets opB(a, b) (mapchain.hip trace_weight)
     std::vector<cd> w(n);
     for (size_t r = 0; r < n; ++r) w[r] = C(in.opB)[r / p.dim + (r % p.dim) * (size_t)p.dim];
     struct { double2 *E, *U, *w, *opA, *opB, *opC, *X[2], *res; int* pos; } d{};
     auto carve = [&](Carve& c) {
-        d.E = c.take<double2>((size_t)Q * m2); d.U = c.take<double2>((size_t)Q * n); d.w = c.take<double2>(n);
+        d.E = c.take<double2>(n_dev * m2); d.U = c.take<double2>(n_dev * n); d.w = c.take<double2>(n);
         d.opA = c.take<double2>(n); d.opB = c.take<double2>(n); d.opC = c.take<double2>(n);
         d.X[0] = c.take<double2>(ncol * n); d.X[1] = c.take<double2>(ncol * n);
         d.res = c.take<double2>(nres); d.pos = c.take<int>(n_t);
@@ -2666,33 +2688,45 @@ static int mapchain_wide_run(pqd_ctx* ctx, const MapChainParams& p, const McIn& 
     PageToucher toucher((void*)result, nres * sizeof(double2));
     const size_t vb = n * sizeof(double2);
     const struct { void* dst; const void* src; size_t bytes; } ups[] = {
-        {d.E, in.dmA, (size_t)Q * m2 * sizeof(double2)}, {d.w, w.data(), vb}, {d.opA, in.opA, vb}, {d.opB, in.opB, vb},
+        {d.E, maps, n_up * m2 * sizeof(double2)}, {d.E + n_up * m2, last, last ? m2 * sizeof(double2) : 0},
+        {d.w, w.data(), vb}, {d.opA, in.opA, vb}, {d.opB, in.opB, vb},
         {d.opC, in.opC, vb}, {d.X[0] + n_t * n, in.rho_init, vb}, {d.pos, pos.data(), n_t * sizeof(int)}};
     for (const auto& u : ups)
         if (u.bytes) HIPCHK(hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, s));
     int launches = 0;
     HIPCHK(hipEventRecord(ev.ev[0], s));
-    if (p.n_tau > 0 && Q > 0) {
-        HIPCHK(launch_mcw_weights(d.E, d.w, d.U, (int)n, Q, s));
+    if (p.n_tau > 0 && n_dev > 0) {
+        HIPCHK(launch_mcw_weights(d.E, d.w, d.U, (int)n, (int)n_dev, s));
         ++launches;
     }
     for (int q = 0; q <= Q; ++q) {
-        const McwPos& r = sch[q];
+        const McwBlockPos& r = sch[q];
         double2 *Xr = d.X[q & 1], *Xw = d.X[(q + 1) & 1];
         if (r.spawn_hi > r.spawn_lo) {
             HIPCHK(launch_mcw_spawn({d.opA, d.opB, d.opC, Xr, d.res, p.dim, (int)n, p.n_t, r.spawn_lo},
                                     r.spawn_hi - r.spawn_lo, s));
             ++launches;
         }
-        if (q < Q && (r.live_hi > r.live_lo || r.trunk)) {
+        auto family = [&](int lo, int hi, int trunk, int map) {
+            const size_t k = std::min((size_t)map, n_up);
             McwStep st{};
-            st.E = d.E + (size_t)q * m2; st.u = p.n_tau > 0 ? d.U + (size_t)q * n : nullptr;
+            st.E = d.E + k * m2; st.u = p.n_tau > 0 ? d.U + k * n : nullptr;
             st.X = Xr; st.Y = Xw; st.pos = d.pos; st.result = d.res;
             st.n = (int)n; st.q = q; st.n_tau = p.n_tau; st.n_t = p.n_t;
-            st.c0 = r.live_lo; st.c1 = r.live_hi; st.trunk = r.trunk;
-            HIPCHK(launch_mcw_step(st, s));
-            ++launches;
-        }
+            st.c0 = lo; st.c1 = hi; st.trunk = trunk;
+            return st;
+        };
+        const bool ring = r.ring_hi > r.ring_lo, str = r.str_hi > r.str_lo || r.trunk;
+        if (q == Q || !(ring || str)) continue;
+        // one product when only one cursor has a live column or both name the same map (mcw_live leaves out the
+        // columns of the merged range that are not in flight), else the two families in one launch
+        if (ring && str && r.ring_map != r.str_map)
+            HIPCHK(launch_mcw_step2(family(r.ring_lo, r.ring_hi, 0, r.ring_map),
+                                    family(r.str_lo, r.str_hi, r.trunk, r.str_map), s));
+        else
+            HIPCHK(launch_mcw_step(family(ring ? r.ring_lo : r.str_lo, str ? r.str_hi : r.ring_hi, r.trunk,
+                                          str ? r.str_map : r.ring_map), s));
+        ++launches;
     }
     HIPCHK(hipEventRecord(ev.ev[1], s));
     const auto t1 = now();
@@ -2710,6 +2744,17 @@ static int mapchain_wide_run(pqd_ctx* ctx, const MapChainParams& p, const McIn& 
     return PQD_OK;
 }
 
+// mode 0 (checked by mapchain_run, pos from choose_blocked) on that driver: one cursor, map q at position q, every
+// trajectory and the trunk in the straight family; the Q maps the sweep reads are uploaded
+static int mapchain_wide_mode0(pqd_ctx* ctx, const MapChainParams& p, const McIn& in, const std::vector<int>& pos,
+                               const McEnv& env, pqd_c128* result) {
+    const std::vector<McwPos> one = mc_wide_schedule(pos, p.n_tau);
+    std::vector<McwBlockPos> sch(one.size());
+    for (size_t q = 0; q < one.size(); ++q)
+        sch[q] = {0, 0, 0, one[q].live_lo, one[q].live_hi, one[q].trunk, (int)q, one[q].spawn_lo, one[q].spawn_hi};
+    return mapchain_wide_run(ctx, p, in, pos, sch, in.dmA, (size_t)Q_of(pos, p.n_tau), nullptr, env, result);
+}
+
 static int mapchain_run(pqd_ctx* ctx, MapChainParams& p, const McIn& in, pqd_c128* result) {
     if (!ctx || !in.rho_init || !in.opA || !in.opB || !in.opC || !in.time || !in.time_sparse || !result || !in.dmA)
         return fail(PQD_ERR_ARG, "NULL argument");
@@ -2724,7 +2769,7 @@ static int mapchain_run(pqd_ctx* ctx, MapChainParams& p, const McIn& in, pqd_c12
     bool blocked;
     std::vector<int> pos;
     if (int rc = choose_blocked(p, env, in, blocked, pos)) return rc;
-    if (mc_wide(p, env)) return mapchain_wide_run(ctx, p, in, pos, env, result);
+    if (mc_wide(p, env)) return mapchain_wide_mode0(ctx, p, in, pos, env, result);
     // every device buffer of the call carved from the context's arena
     const size_t N2 = p.N2, m2 = N2 * N2;
     auto carve = [&](Carve& c) {
@@ -2899,6 +2944,72 @@ int pqd_mc_wide_timing(pqd_ctx* ctx, double* ms_kernel, int32_t* launches) {
     *ms_kernel = ctx->mcw_ms;
     *launches = ctx->mcw_launches;
     return PQD_OK;
+}
+
+// the checks of the block arguments that pqd_calc_onetime_parallel_block_wide and pqd_mc_wide_block_schedule share,
+// then the trunk ends and the schedule
+static int block_schedule(const double* time, int n_tfull, const double* time_sparse, int n_t, int n_tb, int nx_tau,
+                          int n_map, std::vector<int>& pos, std::vector<McwBlockPos>& sch) {
+    if (n_map < 1 || n_tb < 1 || nx_tau < 0) return fail(PQD_ERR_ARG, "bad block sizes");
+    if (n_t < 1 || n_tfull < 1) return fail(PQD_ERR_ARG, "bad sizes");
+    MapChainParams p{};
+    p.n_t = n_t; p.n_tfull = n_tfull;
+    McIn in{};
+    in.time = time; in.time_sparse = time_sparse;
+    pos = trunk_positions(p, in);
+    if ((long long)pos.back() + (long long)n_tb * nx_tau >= INT_MAX)
+        return fail(PQD_ERR_ARG, "positions do not fit an int");
+    sch = mc_wide_block_schedule(pos, n_tb, n_tb * nx_tau, n_map);
+    return PQD_OK;
+}
+
+int pqd_mc_wide_block_schedule(const double* time, int32_t n_tfull, const double* time_sparse, int32_t n_t,
+                               int32_t n_tb, int32_t nx_tau, int32_t n_map, int32_t* pos, int32_t* n_rows,
+                               int32_t* sched, int32_t sched_rows) {
+    if (!time || !time_sparse || !n_rows) return fail(PQD_ERR_ARG, "NULL argument");
+    std::vector<int> ps;
+    std::vector<McwBlockPos> sch;
+    if (int rc = block_schedule(time, n_tfull, time_sparse, n_t, n_tb, nx_tau, n_map, ps, sch)) return rc;
+    if (pos) std::copy(ps.begin(), ps.end(), pos);
+    *n_rows = (int32_t)sch.size();
+    if (!sched) return PQD_OK;
+    if ((size_t)std::max(sched_rows, 0) < sch.size())
+        return fail(PQD_ERR_ARG, "sched holds %d rows, the schedule has %zu", sched_rows, sch.size());
+    for (size_t q = 0; q < sch.size(); ++q) {
+        const McwBlockPos& r = sch[q];
+        const int32_t row[9] = {r.ring_lo, r.ring_hi, r.ring_map, r.str_lo, r.str_hi, r.trunk, r.str_map, r.spawn_lo,
+                                r.spawn_hi};
+        std::copy(row, row + 9, sched + 9 * q);
+    }
+    return PQD_OK;
+}
+
+int pqd_calc_onetime_parallel_block_wide(pqd_ctx* ctx, const pqd_c128* dm_block, const pqd_c128* dm_s,
+                                         const pqd_c128* rho_init, int32_t n_tb, int32_t nx_tau, int32_t n_map,
+                                         int32_t n_t, int32_t n_tfull, int32_t dim, const pqd_c128* opA,
+                                         const pqd_c128* opB, const pqd_c128* opC, const double* time,
+                                         const double* time_sparse, pqd_c128* result) {
+    if (!dm_s) return fail(PQD_ERR_ARG, "dm_s is NULL");
+    if (n_map < 1 || n_tb < 1 || nx_tau < 0) return fail(PQD_ERR_ARG, "bad block sizes");
+    if (!ctx || !rho_init || !opA || !opB || !opC || !time || !time_sparse || !result || !dm_block)
+        return fail(PQD_ERR_ARG, "NULL argument");
+    if (!check_dim_2_24(dim)) return fail(PQD_ERR_UNSUPPORTED, "dim %d not in [2, %d]", dim, HB_NMAX);
+    std::vector<int> pos;
+    std::vector<McwBlockPos> sch;
+    if (int rc = block_schedule(time, n_tfull, time_sparse, n_t, n_tb, nx_tau, n_map, pos, sch)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    MapChainParams p{};
+    p.mode = 1; p.dim = dim; p.N2 = dim * dim; p.n_t = n_t; p.n_tfull = n_tfull; p.n_tau = n_tb * nx_tau;
+    p.n_map = n_map; p.n_tb = n_tb; p.nx_tau = nx_tau;
+    // the block maps the steps read: a prefix of dm_block, up to the highest index a step with a live column names
+    int n_up = 0;
+    for (size_t q = 0; q + 1 < sch.size(); ++q) {
+        const McwBlockPos& r = sch[q];
+        if (r.ring_hi > r.ring_lo && r.ring_map < n_map) n_up = std::max(n_up, r.ring_map + 1);
+        if ((r.str_hi > r.str_lo || r.trunk) && r.str_map < n_map) n_up = std::max(n_up, r.str_map + 1);
+    }
+    const McIn in{dm_block, nullptr, nullptr, dm_s, rho_init, opA, opB, opC, (size_t)n_map, 0, 0, time, time_sparse};
+    return mapchain_wide_run(ctx, p, in, pos, sch, dm_block, (size_t)n_up, dm_s, read_mc_env(), result);
 }
 
 int pqd_map_tail(pqd_ctx* ctx, const pqd_c128* M, int32_t N2, const pqd_c128* X, int32_t n_x, const pqd_c128* w,

@@ -104,6 +104,10 @@ def tls_composite_ops(cavs, sensors, gamma_e, lindblad, rf, laser_cav_coupl, eps
 def _run_composite(prefix, built, t_start, t_end, pulses, options, initial, output_ops, pulse_file, **kw):
     system_op, boson_op, lindblad_ops, interaction_ops, rf_op, initial0, output_ops0 = built
     fwd = {k: options[k] for k in _FWD if k in options}
+    if pulse_file is None:
+        # Purity and Indistinguishability hand every system its pulse train as pulse_file_x (tls takes it the same way);
+        # the wrappers that name the argument pulse_file used to drop it with the other unknown keywords
+        pulse_file = options.get("pulse_file_x")
     return system_ace_stream(
         t_start, t_end, *pulses, pulse_file_x=pulse_file, system_prefix=prefix, threshold="10", threshold_ratio="0.3",
         buffer_blocksize="-1", dict_zero="16", precision="12", boson_e_max=7, system_op=system_op, boson_op=boson_op,

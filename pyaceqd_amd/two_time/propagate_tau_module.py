@@ -4,6 +4,8 @@ Same function names, positional order and keywords as the f2py wrappers the refe
 (correlations.py:534/583/782/831, purity.py:602/709/741/770): Fortran-ordered complex128 inputs,
 hidden dimensions optional (inferred from the shapes, as f2py does), results returned Fortran-ordered.
 """
+import os
+
 import numpy as np
 
 from .. import _lib
@@ -70,9 +72,8 @@ def calc_onetime_parallel(dm_tl, rho_init, n_tau, dim, opa, opb, opc, time, time
     return out
 
 
-def calc_onetime_parallel_block(dm_block, dm_s, rho_init, n_tb, nx_tau, dim, opa, opb, opc, time, time_sparse,
-                                n_map=None, n_t=None, n_tfull=None):
-    """periodic map blocks + stationary map (propagate_tau.f90:189-295)"""
+def _onetime_block(entry, dm_block, dm_s, rho_init, n_tb, nx_tau, dim, opa, opb, opc, time, time_sparse, n_map, n_t,
+                   n_tfull):
     dm_block, dm_s, rho_init = _c(dm_block), _c(dm_s), _c(rho_init)
     opa, opb, opc = _c(opa), _c(opb), _c(opc)
     time, time_sparse = _r(time), _r(time_sparse)
@@ -82,10 +83,30 @@ def calc_onetime_parallel_block(dm_block, dm_s, rho_init, n_tb, nx_tau, dim, opa
     out = np.zeros((n_t, n_tb * nx_tau + 1), dtype=np.complex128, order="F")
     ctx = _ctx()
     with ctx.lock:
-        _lib.check(_lib.lib().pqd_calc_onetime_parallel_block(
+        _lib.check(getattr(_lib.lib(), entry)(
             ctx.handle, _p(dm_block), _p(dm_s), _p(rho_init), int(n_tb), int(nx_tau), int(n_map), int(n_t),
             int(n_tfull), int(dim), _p(opa), _p(opb), _p(opc), _lib.fptr(time), _lib.fptr(time_sparse), _p(out)))
     return out
+
+
+def calc_onetime_parallel_block(dm_block, dm_s, rho_init, n_tb, nx_tau, dim, opa, opb, opc, time, time_sparse,
+                                n_map=None, n_t=None, n_tfull=None, wide=None):
+    """periodic map blocks + stationary map (propagate_tau.f90:189-295)
+
+    dim <= 6 runs as it always did. Above, the call is refused unless opted in: wide=True (or PQD_WIDE_MAPS=1 with
+    wide=None; wide=False never opts in) sends dim 7..24 to calc_onetime_parallel_block_wide."""
+    if wide is None:
+        wide = os.environ.get("PQD_WIDE_MAPS") == "1"
+    entry = "pqd_calc_onetime_parallel_block_wide" if wide and dim > 6 else "pqd_calc_onetime_parallel_block"
+    return _onetime_block(entry, dm_block, dm_s, rho_init, n_tb, nx_tau, dim, opa, opb, opc, time, time_sparse, n_map,
+                          n_t, n_tfull)
+
+
+def calc_onetime_parallel_block_wide(dm_block, dm_s, rho_init, n_tb, nx_tau, dim, opa, opb, opc, time, time_sparse,
+                                     n_map=None, n_t=None, n_tfull=None):
+    """calc_onetime_parallel_block at dim 2..24, always on the sweep by position (csrc/mapchain_wide.hip)"""
+    return _onetime_block("pqd_calc_onetime_parallel_block_wide", dm_block, dm_s, rho_init, n_tb, nx_tau, dim, opa,
+                          opb, opc, time, time_sparse, n_map, n_t, n_tfull)
 
 
 def calc_twotime_phonon_block(dm_taucs2, dm_sep1, dm_sep2, dm_s, rho_init, n_tb, nx_tau, dim, opa, opb, opc, time,

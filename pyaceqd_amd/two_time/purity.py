@@ -339,7 +339,8 @@ class Indistinguishability(Purity):
         G = propagate_tau_module.calc_onetime_parallel_block(
             dm_block=np.asfortranarray(self.tl_dms.transpose(1, 2, 0)), dm_s=self.tl_map,
             rho_init=self._rho0().reshape(dim ** 2), n_tb=int(self.tb / self.dt), nx_tau=self.factor_tau, dim=dim,
-            opa=opA, opb=opB, opc=opC, time=t_axis, time_sparse=self.t_axis_complete)
+            opa=opA, opb=opB, opc=opC, time=t_axis, time_sparse=self.t_axis_complete,
+            wide=self.options.get("wide_maps"))
         return tau, G
 
     def G2_tl(self):
