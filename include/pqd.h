@@ -311,6 +311,14 @@ int pqd_plan_describe(const pqd_plan* plan, char* buf, int32_t len);
  * always was for every other plan. */
 int pqd_live_rows(int32_t n_sys, const pqd_system* systems, const pqd_c128* rho0, const pqd_traj* traj, uint8_t* live);
 int pqd_plan_live_rows(const pqd_plan* plan, uint8_t* live, int32_t len);
+/* The compact row index in which the lean instance applies the fused column operator F(n) where rows stay zero
+ * (DESIGN.md §4.1). pqd_live_col_map: rho (len bytes) lists the rows with live[a] != 0 in increasing order, then the
+ * others in increasing order; *kc = ceil(n_live / 4), the k-steps of four compact rows the product needs. Host only.
+ * pqd_plan_sweep_colk: the k-steps the plan's fast steps (pqd_plan_sweep_readout) run: 3 where the lean instance runs
+ * partial units (parts=1) with 9 to 12 live rows of 16, else 4 (also PQD_LIVE_COL=0). Results are bit-identical either
+ * way; pqd_plan_describe then ends with " colk=3" behind parts=. */
+int pqd_live_col_map(const uint8_t* live, int32_t len, uint8_t* rho, int32_t* kc);
+int pqd_plan_sweep_colk(const pqd_plan* plan, int32_t* colk);
 /* average kernel durations (ms) of the executions since the last reset (the most recent 64 at most),
  * from HIP events on the launch stream: [0] free-propagator kernel, [1] sweep kernel; n = executions */
 int pqd_plan_timing(pqd_plan* plan, double* ms_free, double* ms_sweep, int32_t* n, int32_t reset);

@@ -118,6 +118,8 @@ _SIGS = {
     "pqd_plan_describe": ([C.c_void_p, C.c_char_p, C.c_int32], C.c_int),
     "pqd_live_rows": ([C.c_int32, C.POINTER(pqd_system), P_C128, C.POINTER(pqd_traj), C.POINTER(C.c_uint8)], C.c_int),
     "pqd_plan_live_rows": ([C.c_void_p, C.POINTER(C.c_uint8), C.c_int32], C.c_int),
+    "pqd_live_col_map": ([C.POINTER(C.c_uint8), C.c_int32, C.POINTER(C.c_uint8), P_I32], C.c_int),
+    "pqd_plan_sweep_colk": ([C.c_void_p, P_I32], C.c_int),
     "pqd_plan_info": ([C.c_void_p, P_I32, P_I32, P_I32, P_I64], C.c_int),
     "pqd_plan_timing": ([C.c_void_p, P_F64, P_F64, P_I32, C.c_int32], C.c_int),
     "pqd_plan_destroy": ([C.c_void_p], None),

@@ -222,6 +222,11 @@ struct SweepParams {
                              //   2, g0 a multiple of ng, 16 columns each) of the row, followed by one whole one-row unit.
                              //   The PT phase then has a barrier between the partial units' reads of their rows and the
                              //   writes of their columns (pt_sweep.hip LeanPt::run_parts). No other instance sees such a list
+    int lean_colk;           // k-steps of the lean instance's fused column phase (pt_sweep.hip LeanCol): 4, or 3 where the
+                             //   plan runs partial units, 9 to 12 rows are live and PQD_LIVE_COL is not 0: F(n) is then
+                             //   applied in the compact row index of lean_rho (pqd_host.cpp live_col_map)
+    unsigned long long lean_rho;  // lean_colk == 3: nibble c is rho(c) < 16, the c-th live row in increasing order, then the
+                             //   rows that stay zero in increasing order; else 0 and not read
 };
 
 // split groups with several trajectories per group (pt_msplit.hip)

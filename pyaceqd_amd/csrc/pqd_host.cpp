@@ -505,7 +505,7 @@ void pqd_pt_destroy(pqd_pt* pt) { delete pt; }
 // each has one field.
 struct PlanEnv {
     int split, msplit, ms_tb, ms_ptm, fp4, fpm, pt_mode, cmul3, trpre, bt, colbig, trunk, quad, qpw, qcg, qprio, win,
-        rowpair, ablate, hbpt_g, live_rows, live_part;
+        rowpair, ablate, hbpt_g, live_rows, live_part, live_col;
     bool ms_l2, split_ow, split_gran, split_xcd, sweep_lean, lean_ro, lean_stage, pt_mode_set, fuse, branch, idle, unitbal, split_l2, hilbert;
     unsigned split_spin;
 };
@@ -545,6 +545,7 @@ static PlanEnv read_plan_env() {
     v.unitbal = num("PQD_UNITBAL", 1) != 0;     // PT row units split to balance the waves (0: whole units)
     v.live_rows = num("PQD_LIVE_ROWS", 1);      // PT rows that stay exactly zero get no unit (0: all rows; 2: and verify M, F)
     v.live_part = num("PQD_LIVE_PART", 1) != 0;  // ... and the lean instance deals the live rows in quarters (0: whole rows)
+    v.live_col = num("PQD_LIVE_COL", 1) != 0;    // ... and applies F(n) in their compact index, 3 k-steps (0: all 4)
     v.rowpair = set("PQD_ROWPAIR") ? num("PQD_ROWPAIR", 1) != 0 : -1;  // 0: one PT row per unit; -1 unset
     v.ablate = num("PQD_ABLATE", 0);            // kernel phase ablation and stamps (raw value; measurements only)
     const char* spin = getenv("PQD_SPLIT_SPIN");
@@ -813,6 +814,20 @@ static std::vector<int4> lean_part_units(const std::vector<int>& gmap, int NW, c
     return out;
 }
 
+// The compact row index of the lean instance's column phase (pt_sweep.hip LeanCol): rho lists the live
+// rows in increasing order, then the rows that stay zero in increasing order, and the product F(n) S needs
+// KC = ceil(n_live / 4) k-steps of four compact rows. Increasing order is what keeps the states bit-identical: every
+// live row receives its live products in the order the uncompacted product adds them.
+static int live_col_map(const std::vector<uint8_t>& live, std::vector<uint8_t>& rho) {
+    rho.clear();
+    for (size_t a = 0; a < live.size(); ++a)
+        if (live[a]) rho.push_back((uint8_t)a);
+    const int n_live = (int)rho.size();
+    for (size_t a = 0; a < live.size(); ++a)
+        if (!live[a]) rho.push_back((uint8_t)a);
+    return (n_live + 3) / 4;
+}
+
 // Shared trunks inside a lock-step block (the reference re-propagates 0 -> t1 in every trajectory of a two-time
 // sweep: correlations.py:155-169, pol_entanglement/G2.py:486-497). j[t] = the last step at whose top (before its
 // outputs) trajectory t still holds the MTO-free state: its first MTO's step if that MTO applies after the output,
@@ -957,6 +972,8 @@ static void finalize_trunks(pqd_plan* P) {
     k.ck_map = P->tk_ckmap.p; k.ck_stride = P->n_steps + 1;
     k.lean = 0;
     k.lean_parts = 0;
+    k.lean_colk = 4;
+    k.lean_rho = 0;
     k.blk_fast = nullptr;
     k.blk_stage = nullptr;
     const int nw = P->tk_BT * sweep_wpt(P->N2, P->tk_BT, P->CHI);
@@ -1651,6 +1668,21 @@ static int fill_sweep_params(pqd_plan* P, const pqd_pt* pt, const PlanEnv& env, 
     sp.lean = sweep_lean_ok(P, sp, env) ? 1 : 0;
     if (sp.lean_parts && !sp.lean)  // partial units are read by the lean instance alone (asked above with these fields)
         return fail(PQD_ERR_UNSUPPORTED, "internal: a unit list with partial units outside the lean instance");
+    // the lean instance's column phase in the compact index of the live rows: 3 k-steps instead of 4 where 9 to 12 rows
+    // are live. lean_part_units returns a list for exactly these counts (Tq = 5 or 6 quarters per wave; 13 and 14 do not
+    // fit one partial unit per wave), and the compacted code exists in the instance for partial units only, so any other
+    // plan keeps all four k-steps (PQD_LIVE_COL=0: every plan)
+    sp.lean_colk = 4;
+    sp.lean_rho = 0;
+    if (sp.lean && sp.lean_parts && env.live_col && P->live.size() == 16) {
+        std::vector<uint8_t> rho;
+        int n_live = 0;
+        for (uint8_t v : P->live) n_live += v != 0;
+        if (n_live >= 9 && n_live <= 12 && live_col_map(P->live, rho) == 3) {
+            sp.lean_colk = 3;
+            for (int c = 0; c < 16; ++c) sp.lean_rho |= (unsigned long long)(rho[c] & 15) << (4 * c);
+        }
+    }
     // the lean instance's readout inside the fused column phase (PQD_LEAN_RO=0: the closure pass on every step). The
     // table is the plan's last allocation, so the buffers before it lie where they did
     if (sp.lean && env.lean_ro) {
@@ -2246,6 +2278,21 @@ int pqd_plan_sweep_readout(const pqd_plan* P, int32_t* on) {
     return PQD_OK;
 }
 
+int pqd_plan_sweep_colk(const pqd_plan* P, int32_t* colk) {
+    if (!P || !colk) return fail(PQD_ERR_ARG, "NULL argument");
+    *colk = (P->sp.lean && P->lean_ro && !P->nopt && !P->split && !P->msplit && !P->quad) ? P->sp.lean_colk : 4;
+    return PQD_OK;
+}
+
+int pqd_live_col_map(const uint8_t* live, int32_t len, uint8_t* rho, int32_t* kc) {
+    if (!live || !rho || !kc) return fail(PQD_ERR_ARG, "NULL argument");
+    if (len < 1 || len > 256) return fail(PQD_ERR_ARG, "pqd_live_col_map: len %d outside 1 .. 256", len);
+    std::vector<uint8_t> r;
+    *kc = live_col_map(std::vector<uint8_t>(live, live + len), r);
+    std::copy(r.begin(), r.end(), rho);
+    return PQD_OK;
+}
+
 int pqd_plan_sweep_stage(const pqd_plan* P, int32_t* n_blocks) {
     if (!P || !n_blocks) return fail(PQD_ERR_ARG, "NULL argument");
     *n_blocks = (P->sp.lean && P->lean_ro && !P->nopt && !P->split && !P->msplit && !P->quad) ? P->n_stage : 0;
@@ -2280,7 +2327,10 @@ int pqd_plan_describe(const pqd_plan* P, char* buf, int32_t len) {
     bool dead = false;
     for (size_t a = 0; a < P->live.size(); ++a) { mask |= (uint64_t)(P->live[a] != 0) << a; dead = dead || !P->live[a]; }
     if (dead) {
-        const int m = snprintf(buf + n, (size_t)(len - n), " live=%llx parts=%d", (unsigned long long)mask, sp.lean_parts);
+        int32_t colk = 4;
+        (void)pqd_plan_sweep_colk(P, &colk);
+        const int m = snprintf(buf + n, (size_t)(len - n), colk == 3 ? " live=%llx parts=%d colk=3" : " live=%llx parts=%d",
+                               (unsigned long long)mask, sp.lean_parts);
         if (m < 0 || m >= len - n)
             return fail(PQD_ERR_ARG, "pqd_plan_describe: the line needs %d bytes, len is %d", n + m + 1, len);
     }

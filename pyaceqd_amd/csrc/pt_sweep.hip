@@ -886,6 +886,22 @@ __device__ __forceinline__ double2 lean_row_sum(double2 v) {
     return c_add(v, make_double2(lean_dpp<0x140>(v.x), lean_dpp<0x140>(v.y)));  // row_mirror
 }
 
+// The compaction map of the lean column phase (SweepParams::lean_rho, pqd_host.cpp live_col_map): rho(c), c < 16, one
+// nibble each, the live rows in increasing order followed by the rows that stay zero; every value is < 16.
+__device__ __forceinline__ int lean_rho(unsigned long long rho, int c) { return (int)(rho >> (4 * c)) & 15; }
+// A lane's addresses in the compacted column phase (LeanCol, KC < 4), fixed for the launch: cb[ks] = S[rho(4 ks + lk)][li]
+// of the wave's trajectory (its B operand of compact k-step ks and, as accumulator ks, the row it writes), fo[ks] =
+// rho(li) * 16 + rho(4 ks + lk), its element of F(n) where that is loaded from memory. Nothing at KC = 4.
+typedef double lean_dbl2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) lean_dbl2 LeanLdsC2;
+template <int KC>
+struct LeanColMap {
+    LeanLdsC2* cb[KC];
+    int fo[KC];
+};
+template <>
+struct LeanColMap<4> {};
+
 // The column operands of the lean instance's next fast step, staged in LDS while the PT phase runs (the fast region of
 // the step loop). LeanCol opens with 4 + 4 + 4 n_out loads per lane of bytes that are new every step, directly behind the
 // barrier that ends the PT phase: both waves of every SIMD wait out that round trip together before their first MFMA.
@@ -929,13 +945,22 @@ struct LeanStage {
     static __device__ __forceinline__ LdsC2* area(double2* smem) { return (LdsC2*)(smem + OFF); }
     // the wave's part, fixed for the launch: the lane's byte offset into its piece's source (F: row li, column
     // 4 wave + lk; closure vector and W: element lane), the piece's LDS byte address, the lanes that load
-    static __device__ __forceinline__ unsigned lane_off(int wave, int lane) {
-        return (unsigned)((wave < 4 ? (lane & 15) * N2 + 4 * wave + (lane >> 4) : lane) * sizeof(double2));
+    // KC < 4 (compacted column phase, LeanCol): waves 0..KC-1 source F[rho(li) * 16 + rho(4 wave + lk)], the element
+    // lane (li, lk) multiplies in compact k-step `wave`; wave 3 stages nothing (rho < 16: a row and a column of F(m))
+    template <int KC = 4>
+    static __device__ __forceinline__ unsigned lane_off(int wave, int lane, unsigned long long rho = 0) {
+        if constexpr (KC == 4)
+            return (unsigned)((wave < 4 ? (lane & 15) * N2 + 4 * wave + (lane >> 4) : lane) * sizeof(double2));
+        else
+            return (unsigned)((wave < KC ? lean_rho(rho, lane & 15) * N2 + lean_rho(rho, 4 * wave + (lane >> 4)) : lane) *
+                              sizeof(double2));
     }
     static __device__ __forceinline__ unsigned dst(double2* smem, int wave) {
         return (unsigned)(size_t)(area(smem) + 64 * (wave < 6 ? wave : 0));
     }
+    template <int KC = 4>
     static __device__ __forceinline__ unsigned long long lanes(int wave, int n_out) {
+        if (KC < 4 && wave >= KC && wave < 4) return 0ull;
         return wave < 5 ? ~0ull : wave > 5 ? 0ull : n_out >= KMAX ? ~0ull : (1ull << (N2 * n_out)) - 1;
     }
     // the source of the wave's piece for step m: Fm, Wm: F(m), W(m) of the block's system; cv: the closure vector step m
@@ -982,11 +1007,23 @@ struct LeanStageOp {
 // STAGED: Fn, cv and Wn are the parts of the LDS area LeanStage filled during the PT phase before (F in fragment order,
 // element 64 ks + lane; the closure vector and W as in memory, the same indices as the global loads: < 64 and
 // < 16 n_out <= 64), the same values in the same registers, so nothing downstream differs.
-template <int RS, bool READOUT, bool STAGED = false>
+// KC: k-steps of the product. 4: all 16 rows, the code as it always was. 3 (plans whose 9 to 12 live rows the host
+// compacted, SweepParams::lean_colk): the lane's MFMA operands are those of the compact index, A = F[rho(li)][rho(4 ks + lk)],
+// B = S[rho(4 ks + lk)][16 nt + li], accumulator j < KC is row rho(lk + 4 j), written to the address it was read from
+// (cm.cb[j]); accumulator 3 would be rows that stay zero and is not written. rho is increasing on the live rows and the
+// f64 MFMA adds its k products as one ordered chain of FMAs (scripts/ubench_mfma_f64_korder.hip), so every live row
+// gets the same products in the same order as at KC = 4, less terms that are exactly 0: the same bits. The outputs are
+// then read from values loaded a second time in the layout of KC = 4 (rows 4 ks + lk through sb), with the same MACs
+// in the same order: rows that stay zero add fma(w, 0, t) = t. Those loads of tile nt stand before the tile's writes in
+// program order, and a wave's LDS operations complete in order, so they see the state before F(n) as the operands do.
+// Bounds at KC = 3: rho < 16, so cm.cb[ks] + 16 nt is row rho < 16, column 16 nt + li < 64 of the wave's own trajectory
+// and cm.fo[ks] < 256 an element of F(n); W and the closure vector are indexed as at KC = 4.
+template <int RS, bool READOUT, bool STAGED = false, int KC = 4>
 struct LeanCol {
     static constexpr int N2 = 16, CHI = 64, KS = 4, NTL = 4, KMAX = 4;   // KMAX: the lean instance's limit on n_out
-    typedef double dbl2 __attribute__((ext_vector_type(2)));
-    typedef __attribute__((address_space(3))) dbl2 LdsC2;
+    static_assert(KC == 3 || KC == 4, "three compact k-steps (9 to 12 live rows) or all four");
+    typedef lean_dbl2 dbl2;
+    typedef LeanLdsC2 LdsC2;
     static_assert((12 * RS + 48) * 16 + 15 < 65536, "tile and row offsets fit the DS immediate");
     // where the operands come from: global memory (restrict: nothing here writes it), or the staging area
     template <bool S, typename = void> struct SrcOf { typedef const double2* __restrict__ type; };
@@ -996,17 +1033,27 @@ struct LeanCol {
         const auto v = q[i];
         return make_double2(v.x, v.y);
     }
+    // the lane's B operand of k-step ks, tile nt (and where accumulator ks of that tile goes)
+    static __device__ __forceinline__ LdsC2* opd(LdsC2* sb, const LeanColMap<KC>& cm, int ks, int nt) {
+        if constexpr (KC == 4) return sb + 4 * ks * RS + 16 * nt;
+        else return cm.cb[ks] + 16 * nt;
+    }
 
     // (W(n) stays loaded ahead of the tiles in both forms: read from the staging area behind the last tile's operands
     // instead, it measured the same)
     // Fn: F(n) of the wave's system; cv: closure vector of the slice set of step n - 1; Wn: W(n) of the wave's system;
-    // sb: the lane's LDS base; out: where the slot's n_out outputs of step n go (READOUT only)
-    static __device__ __forceinline__ void run(Src Fn, Src cv, Src Wn, int n_out, LdsC2* sb, double2* out, int lane) {
+    // sb: the lane's LDS base; cm: its compacted addresses (KC < 4); out: where the slot's n_out outputs of step n go
+    // (READOUT only)
+    static __device__ __forceinline__ void run(Src Fn, Src cv, Src Wn, int n_out, LdsC2* sb, const LeanColMap<KC>& cm,
+                                               double2* out, int lane) {
         const int li = lane & 15, lk = lane >> 4;
-        double2 ac[KS], cl[NTL], w[KMAX][KS];
-        double as[KS];
+        double2 ac[KC], cl[NTL], w[KMAX][KS];
+        double as[KC];
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) ac[ks] = ld(Fn, STAGED ? 64 * ks + lane : li * N2 + 4 * ks + lk);
+        for (int ks = 0; ks < KC; ++ks) {
+            if constexpr (KC == 4) ac[ks] = ld(Fn, STAGED ? 64 * ks + lane : li * N2 + 4 * ks + lk);
+            else ac[ks] = ld(Fn, STAGED ? 64 * ks + lane : cm.fo[ks]);
+        }
         if constexpr (READOUT) {
 #pragma unroll
             for (int nt = 0; nt < NTL; ++nt) cl[nt] = ld(cv, 16 * nt + li);
@@ -1018,36 +1065,49 @@ struct LeanCol {
                 }
         }
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) as[ks] = ac[ks].x + ac[ks].y;
+        for (int ks = 0; ks < KC; ++ks) as[ks] = ac[ks].x + ac[ks].y;
         double2 r[KS];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) r[ks] = c_zero();
-        // a tile's four operand values are read while the tile before it runs its MFMAs (one LDS round trip exposed per
+        // a tile's operand values are read while the tile before it runs its MFMAs (one LDS round trip exposed per
         // step, not one per value; tiles are disjoint columns, so the in-place writes of a tile touch nothing read later)
-        dbl2 bn[KS];
+        dbl2 bn[KC];
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) bn[ks] = sb[4 * ks * RS];
+        for (int ks = 0; ks < KC; ++ks) bn[ks] = *opd(sb, cm, ks, 0);
 #pragma unroll
         for (int nt = 0; nt < NTL; ++nt) {
             dbl4 p1 = dbl4{0, 0, 0, 0}, p2 = p1, p3 = p1;
-            dbl2 bq[KS];
+            dbl2 bq[KC], bo[KS];
+            // KC < 4: the tile's values in the rows the outputs are summed over, issued ahead of the next tile's operands
+            // and used behind this tile's first MFMAs
+            if constexpr (KC < 4 && READOUT) {
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
+                for (int ks = 0; ks < KS; ++ks) bo[ks] = sb[4 * ks * RS + 16 * nt];
+            }
+#pragma unroll
+            for (int ks = 0; ks < KC; ++ks) {
                 bq[ks] = bn[ks];
-                if (nt + 1 < NTL) bn[ks] = sb[4 * ks * RS + 16 * (nt + 1)];
+                if (nt + 1 < NTL) bn[ks] = *opd(sb, cm, ks, nt + 1);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
+            for (int ks = 0; ks < KC; ++ks) {
                 const dbl2 bv = bq[ks];
                 const double bs = bv.x + bv.y;
                 p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[ks].x, bv.x, p1, 0, 0, 0);
                 p2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[ks].y, bv.y, p2, 0, 0, 0);
                 p3 = __builtin_amdgcn_mfma_f64_16x16x4f64(as[ks], bs, p3, 0, 0, 0);
-                if constexpr (READOUT) c_fma(r[ks], make_double2(bv.x, bv.y), cl[nt]);
+                if constexpr (READOUT) {
+                    if constexpr (KC == 4) c_fma(r[ks], make_double2(bv.x, bv.y), cl[nt]);
+                    else c_fma(r[ks], make_double2(bo[ks].x, bo[ks].y), cl[nt]);
+                }
+            }
+            if constexpr (KC < 4 && READOUT) {
+#pragma unroll
+                for (int ks = KC; ks < KS; ++ks) c_fma(r[ks], make_double2(bo[ks].x, bo[ks].y), cl[nt]);
             }
 #pragma unroll
-            for (int j = 0; j < 4; ++j) sb[4 * j * RS + 16 * nt] = dbl2{p1[j] - p2[j], p3[j] - p1[j] - p2[j]};
+            for (int j = 0; j < KC; ++j) *opd(sb, cm, j, nt) = dbl2{p1[j] - p2[j], p3[j] - p1[j] - p2[j]};
         }
         if constexpr (READOUT) {
             // t[k] over the lane's rows; re[k], im[k] = 0 for k >= n_out
@@ -1348,13 +1408,31 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
                 using LP = LeanPt<CHI, RS, TS, LEAN_PF>;
                 using LS = LeanStage<BT * TS + BT * N2>;
                 const int st_sys = p.blk_stage ? ldc(p.blk_stage + blockIdx.x) : -1;
-                auto fast_steps = [&](auto stc) {
+                // PARTS: kcc is the number of k-steps of the column phase, 3 where the host compacted the live rows
+                // (SweepParams::lean_colk, lean_rho), chosen once per launch like STG
+                auto fast_steps = [&](auto stc, auto kcc) {
                     constexpr bool STG = decltype(stc)::value;
+                    constexpr int KC = decltype(kcc)::value;
+                    static_assert(KC == 4 || PARTS, "compacted rows come with partial units only");
                     typename LS::LdsC2* sg = LS::area(smem);
                     const double2* Fst = p.F + (size_t)(STG ? st_sys : 0) * p.f_stride;
                     const double2* Wst = Wg + (size_t)(STG ? st_sys : 0) * p.w_stride;
-                    const unsigned st_off = LS::lane_off(wave, lane), st_to = LS::dst(smem, wave);
-                    const unsigned long long st_ln = LS::lanes(wave, p.n_out);
+                    const unsigned st_off = LS::template lane_off<KC>(wave, lane, p.lean_rho), st_to = LS::dst(smem, wave);
+                    const unsigned long long st_ln = LS::template lanes<KC>(wave, p.n_out);
+                    // the lane's compacted addresses, pinned like sb (rho < 16: rows of the wave's own trajectory)
+                    LeanColMap<KC> cm;
+                    if constexpr (KC < 4) {
+#pragma unroll
+                        for (int ks = 0; ks < KC; ++ks) {
+                            const int row = lean_rho(p.lean_rho, 4 * ks + pq);
+                            unsigned v = (unsigned)(size_t)((typename LC::LdsC2*)stw + row * RS + pj);
+                            int f = lean_rho(p.lean_rho, pj) * N2 + row;
+                            asm("" : "+v"(v));
+                            asm("" : "+v"(f));
+                            cm.cb[ks] = (typename LC::LdsC2*)v;
+                            cm.fo[ks] = f;
+                        }
+                    }
                     if constexpr (STG) {
                         LS::issue(LS::src(wave, Fst + (size_t)n * N2 * N2, p.closure + (size_t)sc_prev * CHI,
                                           Wst + (size_t)n * p.n_out * N2), st_off, st_to, st_ln);
@@ -1374,17 +1452,18 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
                             const bool inwin = w_beg <= n && n <= w_end;   // the store's predicate: the slot's window, wave-uniform
                             if constexpr (STG) {
                                 if (inwin)
-                                    LeanCol<RS, true, true>::run(sg + LS::F_AT, sg + LS::C_AT, sg + LS::W_AT, p.n_out, sb,
-                                                                 outg + w_off + (long long)(n - w_beg) * p.n_out, lane);
+                                    LeanCol<RS, true, true, KC>::run(sg + LS::F_AT, sg + LS::C_AT, sg + LS::W_AT, p.n_out, sb, cm,
+                                                                     outg + w_off + (long long)(n - w_beg) * p.n_out, lane);
                                 else
-                                    LeanCol<RS, false, true>::run(sg + LS::F_AT, nullptr, nullptr, 0, sb, nullptr, lane);
+                                    LeanCol<RS, false, true, KC>::run(sg + LS::F_AT, nullptr, nullptr, 0, sb, cm, nullptr, lane);
                             } else {
                                 const double2* Fn = Fg + (size_t)n * N2 * N2;
                                 if (inwin)
-                                    LC::run(Fn, p.closure + (size_t)sc_prev * CHI, Ww + (size_t)n * p.n_out * N2, p.n_out, sb,
-                                            outg + w_off + (long long)(n - w_beg) * p.n_out, lane);
+                                    LeanCol<RS, true, false, KC>::run(Fn, p.closure + (size_t)sc_prev * CHI,
+                                                                      Ww + (size_t)n * p.n_out * N2, p.n_out, sb, cm,
+                                                                      outg + w_off + (long long)(n - w_beg) * p.n_out, lane);
                                 else
-                                    LeanCol<RS, false>::run(Fn, nullptr, nullptr, 0, sb, nullptr, lane);
+                                    LeanCol<RS, false, false, KC>::run(Fn, nullptr, nullptr, 0, sb, cm, nullptr, lane);
                             }
                         }
                         __syncthreads();
@@ -1414,8 +1493,17 @@ __global__ __launch_bounds__(64 * BT * sweep_wpt(N2, BT, CHI)) void pt_sweep_ker
                         sc_cur = sc_nxt;
                     }
                 };
-                if (st_sys >= 0) fast_steps(std::true_type{});
-                else fast_steps(std::false_type{});
+                using KC4 = std::integral_constant<int, 4>;
+                bool compact = false;
+                if constexpr (PARTS) compact = p.lean_colk == 3;
+                if (compact) {
+                    if constexpr (PARTS) {
+                        using KC3 = std::integral_constant<int, 3>;
+                        if (st_sys >= 0) fast_steps(std::true_type{}, KC3{});
+                        else fast_steps(std::false_type{}, KC3{});
+                    }
+                } else if (st_sys >= 0) fast_steps(std::true_type{}, KC4{});
+                else fast_steps(std::false_type{}, KC4{});
                 fz = true;
                 if (tid < ntr) {  // W(n_end - 1) row element for the traces below
                     const int a = tid % N2, bk = tid / N2, b = bk / p.n_out, k = bk - (bk / p.n_out) * p.n_out;

@@ -541,11 +541,20 @@ class Plan:
         _lib.check(_lib.lib().pqd_plan_sweep_stage(self.handle, C.byref(n)))
         return int(n.value)
 
+    def sweep_colk(self):
+        """the k-steps of four rows in which the plan's fast steps (sweep_readout) apply the fused column operator: 3 where
+        the lean instance deals 9 to 12 live rows of 16 in quarters and multiplies them in their compact index
+        (pqd_live_col_map), else 4 (PQD_LIVE_COL=0: always 4). Results are bit-identical either way"""
+        k = C.c_int32()
+        _lib.check(_lib.lib().pqd_plan_sweep_colk(self.handle, C.byref(k)))
+        return int(k.value)
+
     def describe(self):
         """every decision plan creation took (pqd_plan_describe) as a dict of strings: path, workgroup shape, split /
         quad / trunk layout, windows, the A/B switches, and hashes of the block, row-unit and group tables. A plan whose
         sweep leaves out rows that stay zero (live_rows) has two more entries at the end: "live", the mask of the rows it
-        contracts (hex, bit alpha), and "parts", 1 when the lean instance deals them in quarters"""
+        contracts (hex, bit alpha), and "parts", 1 when the lean instance deals them in quarters; and behind them
+        "colk" = 3 where the column phase runs three k-steps (sweep_colk)"""
         buf = C.create_string_buffer(2048)
         _lib.check(_lib.lib().pqd_plan_describe(self.handle, buf, len(buf)))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split())

@@ -44,7 +44,7 @@ SWITCHES = ("PQD_SPLIT", "PQD_SPLIT_GRAN", "PQD_SPLIT_OW", "PQD_SPLIT_XCD", "PQD
             "PQD_MSPLIT", "PQD_MS_L2", "PQD_MS_PTM", "PQD_MS_TB", "PQD_ABLATE", "PQD_FPM", "PQD_QUAD",
             "PQD_MC_BLOCKED", "PQD_MC_PIPE", "PQD_MC_L", "PQD_MC_TIMING",
             "PQD_BT", "PQD_PT_MODE", "PQD_CMUL3", "PQD_COLBIG", "PQD_TRPRE", "PQD_FUSE", "PQD_SWEEP_LEAN", "PQD_LEAN_RO",
-            "PQD_LEAN_STAGE", "PQD_LIVE_PART", "PQD_LIVE_ROWS", "PQD_TRUNK", "PQD_BRANCH")
+            "PQD_LEAN_STAGE", "PQD_LIVE_PART", "PQD_LIVE_COL", "PQD_LIVE_ROWS", "PQD_TRUNK", "PQD_BRANCH")
 SPLIT, MSPLIT = "split groups", "split groups, several trajectories per group"
 BATCHED, QUAD = "batched lock-step sweep", "register-resident TLS quads"
 NOPT = "no PT (one wave per trajectory)"
